@@ -1,8 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     (N > 1: launched by torch.distributed.run, one process per GPU, RCCL)
+
+A plain run sets up the headline step's batch, warms up W steps, times K
+steps and prints the line (`value`, `ms_per_step`).  --dump-outputs DIR then
+writes what the last timed step returned (every cas_id and status, the Object
+write set in row order) as DIR/<name>.npy; the same arguments give the same
+inputs, so two builds compare file for file.  Everything below the headline
+-- the components, `roofline`, `cpu_baseline`, the parity checks against the
+oracle -- runs with --full.
 
 Headline `value` (files/s, whole job): one STEP = one identifier pass over a
 batch resident in HBM -- BASELINE config 2 per GPU (1 M synthetic files,
@@ -11,8 +19,8 @@ consisting of K1 (sampled cas_id of every file), the cas_id -> Object
 grouping of all files of all GPUs (hash-sharded, RCCL all-to-all at N > 1) and
 the Object link batch (K7: create / connect lists).  Weak scaling: every GPU brings its own 1 M files.
 
-Components reported on the same line (each timed the same way, K steps after W
-warm-up, barrier + synchronize on both sides, max over ranks):
+Components reported on the same line with --full (each timed the same way, K
+steps after W warm-up, barrier + synchronize on both sides, max over ranks):
   cas      K1 alone over config 2                              files/s
   dedup    config 4: 12.5 M rows per GPU (100 M at 8 GPUs)     rows/s
            (+ at N = 1 the whole 100 M-row table on one GPU)
@@ -318,7 +326,10 @@ class Runner:
         return self.max_over_ranks(time.perf_counter() - t0)
 
     # ---------------------------------------------------------------- config 2
-    def run_cas(self, steps, warmup):
+    def cas_setup(self):
+        """Config 2 of this rank in HBM and the two timed callables over it: k1
+        (K1 alone) and job (the identifier job step, the headline)."""
+        from types import SimpleNamespace
         torch = self.torch
         from spacedrive_amd import cas, corpus, dedup
         n = self.args.files
@@ -331,8 +342,8 @@ class Runner:
                              device=self.dev).to(torch.int32)
         torch.cuda.synchronize()
         lens = ln.cpu().numpy().view(np.uint32)
-        blk, par = compressions(lens)
-        res = {}
+        # --dump-outputs: what the newest job step returned is kept until job_outputs
+        keep, last = [bool(self.args.dump_outputs)], [None]
 
         def k1():
             cas.cas_batch_device(arena, off, ln, out, st, ctx=self.ctx)
@@ -345,16 +356,72 @@ class Runner:
             if fused:
                 # one GPU: the grouping and the Object write set in one pass
                 # (sdgpu_group_link_device; rows in id order, rank = row)
-                dedup.group_link_device(key, has, None, None, 0, 100, ctx=self.ctx, trim=False)
+                r = dedup.group_link_device(key, has, None, None, 0, 100, ctx=self.ctx, trim=False)
+                last[0] = r if keep[0] else None
                 return
             if self.comm is not None:
                 # N GPUs over libsdgpu's RCCL communicator: the records go to
                 # their owners and each owner writes the write set of the rows
                 # it owns (sdgpu_group_link_sharded_device): no return leg
-                dedup.group_link_sharded(key, has, None, grank, self.comm, 100, trim=False)
+                r = dedup.group_link_sharded(key, has, None, grank, self.comm, 100, trim=False)
+                last[0] = r if keep[0] else None
                 return
             rep = self.group(key, has, grank)
-            dedup.link_batch_device(rep, grank, None, 0, ctx=self.ctx, trim=False)
+            r = dedup.link_batch_device(rep, grank, None, 0, ctx=self.ctx, trim=False)
+            last[0] = r if keep[0] else None
+
+        return SimpleNamespace(n=n, arena=arena, off=off, ln=ln, out=out, st=st, has=has,
+                               lens=lens, k1=k1, job=job, fused=fused, keep=keep, last=last)
+
+    def job_result(self, s, t_job, steps):
+        n, fused = s.n, s.fused
+        return {"value": self.world * n * steps / t_job,
+                "ms_per_step": 1e3 * t_job / steps,
+                "grouping": ("fused group + write set (sdgpu_group_link_device)"
+                             if fused else
+                             "sharded write set, no return leg "
+                             "(sdgpu_group_link_sharded_device)"
+                             if self.comm is not None else
+                             "sharded grouping + link batch (torch.distributed)")}
+
+    def job_outputs(self, s):
+        """What the newest identifier job step handed its caller, as host
+        arrays: every file's cas_id bytes and status (K1) and the Object write
+        set -- creator ranks and (row, creator) connect pairs.  The fused and
+        sharded steps return the set in bucket order; it is put in row order
+        here (dedup.split_link_lists), so two runs compare array for array."""
+        from spacedrive_amd import dedup
+        self.torch.cuda.synchronize()
+        o, s.last[0], s.keep[0] = s.last[0], None, False
+        cnt = [int(x) for x in o[-1].cpu().tolist()]
+        if len(o) == 3:  # (who, obj, [creators, linked, entries])
+            e = cnt[2]
+            create, lrow, lobj = dedup.split_link_lists(o[0][:e].cpu().numpy(),
+                                                        o[1][:e].cpu().numpy())
+        else:  # link_batch_device: (create, link_row, link_obj, [creators, linked])
+            create, lrow, lobj = (o[i][:cnt[min(i, 1)]].cpu().numpy().view(np.uint32)
+                                  for i in range(3))
+        return {"cas_id": s.out.cpu().numpy(), "cas_status": s.st.cpu().numpy(),
+                "object_create": create, "object_link_row": lrow, "object_link_obj": lobj,
+                "object_counts": np.asarray(cnt[:2])}
+
+    def run_job(self, steps, warmup):
+        """The plain run: the identifier job step alone (the headline)."""
+        s = self.cas_setup()
+        t_job = self.timed(s.job, steps, warmup)
+        assert int(s.st.abs().sum()) == 0
+        if self.args.dump_outputs:
+            self._outputs = self.job_outputs(s)
+        return {"job": self.job_result(s, t_job, steps)}
+
+    def run_cas(self, steps, warmup):
+        torch = self.torch
+        from spacedrive_amd import dedup
+        cs = self.cas_setup()
+        n, arena, off, ln, out, st, has = cs.n, cs.arena, cs.off, cs.ln, cs.out, cs.st, cs.has
+        lens, k1, job, fused = cs.lens, cs.k1, cs.job, cs.fused
+        blk, par = compressions(lens)
+        res = {}
 
         # K1 alone, with live per-kernel event timing on its launch stream
         t_cas, kt = self.timed_kernels(k1, steps, warmup)
@@ -373,14 +440,9 @@ class Runner:
         # the communicator's deadline) is reported; K1's rate stays measured.
         try:
             t_job = self.timed(job, steps, warmup)
-            res["job"] = {"value": self.world * n * steps / t_job,
-                          "ms_per_step": 1e3 * t_job / steps,
-                          "grouping": ("fused group + write set (sdgpu_group_link_device)"
-                                       if fused else
-                                       "sharded write set, no return leg "
-                                       "(sdgpu_group_link_sharded_device)"
-                                       if self.comm is not None else
-                                       "sharded grouping + link batch (torch.distributed)")}
+            if self.args.dump_outputs:
+                self._outputs = self.job_outputs(cs)
+            res["job"] = self.job_result(cs, t_job, steps)
         except Exception as e:  # noqa: BLE001 -- reported in the line
             log(f"bench: identifier job step failed: {e!r}")
             res["job"] = {"error": repr(e)[:400]}
@@ -1521,7 +1583,34 @@ def parse_args(argv=None):
                          "(PMC passes: one variant per kernel name)")
     ap.add_argument("--verify", action="store_true",
                     help="check the sharded grouping against the one-GPU grouping first")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg (--components), the roofline and the CPU baselines; "
+                         "without it only the headline step is set up and timed")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed headline step returned to DIR/<name>.npy")
     return ap.parse_args(argv)
+
+
+DUMP_LIMIT = 64_000_000  # bytes of .npy data per --dump-outputs
+
+
+def dump_outputs(path: str, arrays: dict) -> dict:
+    """Writes every array as path/<name>.npy: float32 where that holds the
+    values exactly (bytes, statuses), float64 otherwise (u32 ranks).  Above
+    DUMP_LIMIT in all, each array keeps a fixed seeded sample of its rows (the
+    same rows in every run of the same arguments).  Returns {name: rows}."""
+    os.makedirs(path, exist_ok=True)
+    conv = {k: np.ascontiguousarray(v, np.float32 if v.dtype.itemsize == 1 or k == "cas_status"
+                                    else np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in conv.values())
+    wrote = {}
+    for k, a in conv.items():
+        if total > DUMP_LIMIT and a.shape[0] > 1024:
+            m = max(1024, int(a.shape[0] * 0.98 * DUMP_LIMIT / total))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], m, replace=False))]
+        np.save(os.path.join(path, k + ".npy"), a)
+        wrote[k] = int(a.shape[0])
+    return wrote
 
 
 def main(argv=None, runner_cls=None, out=None):
@@ -1585,6 +1674,25 @@ def main(argv=None, runner_cls=None, out=None):
                                            "RCCL all-to-all"},
                  "world": R.world_info()})
 
+    if not args.full:
+        # the plain run: set up, warm up, time the headline step, print the line
+        if args.components != parse_args([]).components:
+            log("bench: --components takes effect with --full; timing the headline step alone")
+        c = leg("identifier_job", lambda: R.run_job(args.steps, args.warmup))
+        if c:
+            comp["identifier_job"] = c["job"]
+            line["value"] = c["job"]["value"]
+            line["ms_per_step"] = c["job"]["ms_per_step"]
+        if c and args.dump_outputs and R.rank == 0:
+            line["outputs"] = leg("dump_outputs",
+                                  lambda: dump_outputs(args.dump_outputs, R._outputs))
+        walls["total"] = round(time.perf_counter() - t_begin, 2)
+        writer.emit()
+        leg("shutdown", R.shutdown)
+        if line.get("value") is None:
+            sys.exit(3)  # the headline step failed: the line says why
+        return
+
     def peaks():
         v = R.ctx.valu_peak()
         cp = R.ctx.valu_peak(5)  # register-only compressions, 680 VALU each
@@ -1616,6 +1724,10 @@ def main(argv=None, runner_cls=None, out=None):
                 line["ms_per_step"] = c["job"]["ms_per_step"]
             line["kernels"] = c["kernels"]
             line["roofline"] = leg("roofline", lambda: build_roofline(c, pk[1], pk[0], pk[2]))
+            if args.dump_outputs and R.rank == 0 and getattr(R, "_outputs", None):
+                line["outputs"] = leg("dump_outputs",
+                                      lambda: dump_outputs(args.dump_outputs, R._outputs))
+                R._outputs = None
     if "single" in comps:
         single = leg("single_file_latency", R.run_single)
         if single:

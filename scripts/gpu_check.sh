@@ -12,7 +12,7 @@ rc=$?
 tail -3 gpurun_out/${TAG}_pytest.log
 [ $rc -eq 0 ] || { grep -n "FAILED\|Error" gpurun_out/${TAG}_pytest.log | head -20; exit $rc; }
 if [ -n "$BENCH" ]; then
-  timeout -k 10 600 python -u bench.py --gpus 1 --steps 20 --warmup 5 ${BENCHARGS} \
+  timeout -k 10 600 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 ${BENCHARGS} \
     > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || exit 1
   python3 scripts/bench_brief.py gpurun_out/${TAG}_bench.json
 fi

@@ -1,5 +1,5 @@
 # Round checkpoint on one box: the whole GPU test suite,
-# smoke, then the driver's exact bench command (wall-clocked).
+# smoke, then the bench with every leg (--full, wall-clocked).
 #   TAG=r6x bash scripts/gpu_full.sh
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
@@ -12,7 +12,7 @@ tail -3 gpurun_out/${TAG}_pytest.log
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${TAG}_smoke.log 2>&1 || { tail -20 gpurun_out/${TAG}_smoke.log; exit 1; }
 tail -2 gpurun_out/${TAG}_smoke.log
 s=$(date +%s.%N)
-timeout -k 10 600 python -u bench.py --gpus 1 --steps 20 --warmup 5 \
+timeout -k 10 600 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 \
   > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || exit 1
 e=$(date +%s.%N)
 python3 -c "print('bench wall s', $e - $s)"

@@ -15,14 +15,14 @@ if [ -n "$TESTS" ]; then
 fi
 if [ -z "$NOBENCH" ]; then
   s=$(date +%s.%N)
-  timeout -k 10 600 python -u bench.py --gpus 1 --steps 20 --warmup 5 ${BENCHARGS} \
+  timeout -k 10 600 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 ${BENCHARGS} \
     > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || exit 1
   e=$(date +%s.%N)
   python3 -c "print('bench wall s', $e - $s)"
   python3 scripts/bench_brief.py gpurun_out/${TAG}_bench.json
 fi
 if [ -n "$FORCECOMM" ]; then
-  SD_BENCH_FORCE_COMM=1 timeout -k 10 300 python -u bench.py --gpus 1 --steps 20 --warmup 5 \
+  SD_BENCH_FORCE_COMM=1 timeout -k 10 300 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 \
     --components cas --no-cpu > gpurun_out/${TAG}_fc.json 2> gpurun_out/${TAG}_fc.err || exit 1
   python3 scripts/bench_brief.py gpurun_out/${TAG}_fc.json
 fi

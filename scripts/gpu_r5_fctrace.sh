@@ -7,7 +7,7 @@ OUT=gpurun_out/fctrace_$TAG
 mkdir -p "$OUT"
 for fc in 1 0; do
   SD_BENCH_FORCE_COMM=$fc timeout -k 10 300 rocprofv3 --kernel-trace -d "$OUT/fc$fc" -o run \
-    --output-format csv -- python3 bench.py --gpus 1 --steps 6 --warmup 2 --components cas \
+    --output-format csv -- python3 bench.py --full --gpus 1 --steps 6 --warmup 2 --components cas \
     --no-cpu > "$OUT/fc$fc.json" 2> "$OUT/fc$fc.err" || exit 1
   f=$(find "$OUT/fc$fc" -name "run_kernel_trace.csv" | head -1)
   python3 scripts/exp/timeline.py "$f" ${TL_N:-60} > "$OUT/fc${fc}_timeline.txt" || exit 1

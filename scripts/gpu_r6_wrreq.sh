@@ -21,7 +21,7 @@ python3 scripts/exp/pmc_kernels.py "$OUT" > "$OUT/summary.txt" || exit 1
 cat "$OUT/summary.txt"
 if [ -z "$NOVERIFY" ]; then
   for N in 2 3; do
-    SD_BENCH_BACKEND=host timeout -k 10 400 python -u bench.py --gpus $N --steps 3 --warmup 1 \
+    SD_BENCH_BACKEND=host timeout -k 10 400 python -u bench.py --full --gpus $N --steps 3 --warmup 1 \
       --components dedup --dedup-rows 4000000 --no-cpu --verify \
       > "$OUT/verify_host$N.json" 2> "$OUT/verify_host$N.err" || exit 1
     grep "verify:" "$OUT/verify_host$N.err"

@@ -147,7 +147,7 @@ import json, sys
 sys.path.insert(0, sys.argv[1])
 from spacedrive_amd import file_identifier as fi
 from spacedrive_amd._native import Context
-paths = json.loads(sys.argv[2])
+paths = json.load(sys.stdin)  # not argv: one argument holds at most 128 KiB
 ctx = Context(0)
 res = fi.identify(paths, ctx=ctx)
 print(json.dumps({"cas": [bytes(c).hex() for c in res.cas8], "status": [int(s) for s in res.status],
@@ -171,7 +171,7 @@ def test_identify_read_paths_agree(io, files, tmp_path):
     env.pop("SDGPU_IO", None)
     if io != "bounce":
         env["SDGPU_IO"] = io
-    p = subprocess.run([sys.executable, "-c", _IO_CHILD, root, json.dumps(paths)],
+    p = subprocess.run([sys.executable, "-c", _IO_CHILD, root], input=json.dumps(paths),
                        capture_output=True, text=True, timeout=120, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     res = json.loads(p.stdout.strip().splitlines()[-1])
@@ -209,7 +209,7 @@ def test_identify_staging_schedules_agree(env, config1_dir):
     paths, want = config1_dir
     e = {k: v for k, v in os.environ.items() if not k.startswith("SDGPU_")}
     e.update(env)
-    p = subprocess.run([sys.executable, "-c", _IO_CHILD, root, json.dumps(paths)],
+    p = subprocess.run([sys.executable, "-c", _IO_CHILD, root], input=json.dumps(paths),
                        capture_output=True, text=True, timeout=180, env=e)
     assert p.returncode == 0, p.stderr[-3000:]
     res = json.loads(p.stdout.strip().splitlines()[-1])
