@@ -82,6 +82,153 @@ impl ObjectIndex<'_> {
         }
         rc
     }
+
+    // ---- a library-lifetime index (include/sdgpu.h, "ABI 6, additive") --------
+
+    /// The Object owning each cas key, as a grouping's rep shows it (a rank, or
+    /// SDGPU_REP_EXISTING | object id); `sys::SDGPU_INDEX_MISS` for none.  The
+    /// watcher's create path (location/manager/watcher/utils.rs:240-275:
+    /// find_first(object where file_paths.some(cas_id == X))) for one or a
+    /// few keys, without the database.
+    pub fn lookup(&self, keys: &[u64]) -> io::Result<Vec<u32>> {
+        let mut values = vec![sys::SDGPU_INDEX_MISS; keys.len()];
+        check(unsafe {
+            sys::sdgpu_index_lookup(self.0, keys.as_ptr(), keys.len() as u64, values.as_mut_ptr())
+        })?;
+        Ok(values)
+    }
+
+    /// Removes the keys (watcher delete / update paths, utils.rs:746-765: the
+    /// Object is deleted when no file_path is left).  `values` (what `lookup`
+    /// returned): a key goes only while it still holds that value.  Returns
+    /// how many keys were actually removed.
+    pub fn remove(&self, gpu: &Gpu, keys: &[u64], values: Option<&[u32]>) -> io::Result<u32> {
+        if keys.is_empty() {
+            return Ok(0);
+        }
+        if values.map_or(false, |v| v.len() != keys.len()) {
+            return Err(io::Error::from_raw_os_error(22));
+        }
+        let n = keys.len();
+        let dk = DeviceMem::from_slice(gpu, keys)?;
+        let dv = match values {
+            Some(v) => Some(DeviceMem::from_slice(gpu, v)?),
+            None => None,
+        };
+        let dr = DeviceMem::alloc(gpu, 4)?;
+        let stream = unsafe { sys::sdgpu_stream(*gpu.ctx()) };
+        check(unsafe {
+            sys::sdgpu_index_remove_device(self.0, dk.ptr().cast(),
+                                           dv.as_ref().map_or(ptr::null(), |d| d.ptr().cast()),
+                                           n as u64, dr.ptr().cast(), stream)
+        })?;
+        dr.read_u32(gpu)
+    }
+
+    /// Removes every entry of the given Object ids (the orphan remover's
+    /// deletions, core/src/object/orphan_remover.rs:57-90: it knows ids, not
+    /// cas_ids).  `max_id` bounds the ids (it sizes the mark map).  Returns how
+    /// many entries were removed.
+    pub fn remove_objects(&self, gpu: &Gpu, ids: &[i32], max_id: u32) -> io::Result<u32> {
+        if ids.is_empty() {
+            return Ok(0);
+        }
+        let dh = DeviceMem::from_slice(gpu, ids)?;
+        let dr = DeviceMem::alloc(gpu, 4)?;
+        let stream = unsafe { sys::sdgpu_stream(*gpu.ctx()) };
+        check(unsafe {
+            sys::sdgpu_index_remove_objects_device(self.0, dh.ptr().cast(), ids.len() as u64, max_id,
+                                                   dr.ptr().cast(), stream)
+        })?;
+        dr.read_u32(gpu)
+    }
+
+    /// The live entries as (key, value) pairs in no particular order: what a
+    /// host persists at shutdown (its SDGPU_REP_EXISTING entries go back in
+    /// with `add_objects` at the next start).
+    pub fn export(&self, gpu: &Gpu) -> io::Result<Vec<(u64, u32)>> {
+        let mut cap = self.stats()?[0] as usize;
+        loop {
+            let dk = DeviceMem::alloc(gpu, 8 * cap.max(1))?;
+            let dv = DeviceMem::alloc(gpu, 4 * cap.max(1))?;
+            let dc = DeviceMem::alloc(gpu, 4)?;
+            let stream = unsafe { sys::sdgpu_stream(*gpu.ctx()) };
+            check(unsafe {
+                sys::sdgpu_index_export_device(self.0, dk.ptr().cast(), dv.ptr().cast(), cap as u64,
+                                               dc.ptr().cast(), stream)
+            })?;
+            let n = dc.read_u32(gpu)? as usize;
+            if n > cap {
+                cap = n; // grew since the count was read: once more with room
+                continue;
+            }
+            let mut keys = vec![0u64; n];
+            let mut values = vec![0u32; n];
+            dk.read_into(gpu, &mut keys)?;
+            dv.read_into(gpu, &mut values)?;
+            return Ok(keys.into_iter().zip(values).collect());
+        }
+    }
+
+    /// [live keys, slots in use including removed ones, capacity in slots].
+    pub fn stats(&self) -> io::Result<[u64; 3]> {
+        let mut out = [0u64; 3];
+        check(unsafe { sys::sdgpu_index_stats(self.0, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+}
+
+/// A device allocation of the context, freed on drop (staging for the index
+/// maintenance calls above).
+struct DeviceMem<'a> {
+    gpu: &'a Gpu,
+    p: *mut std::os::raw::c_void,
+}
+
+impl<'a> DeviceMem<'a> {
+    fn alloc(gpu: &'a Gpu, bytes: usize) -> io::Result<Self> {
+        let mut p = ptr::null_mut();
+        check(unsafe { sys::sdgpu_alloc_device(*gpu.ctx(), bytes, &mut p) })?;
+        Ok(DeviceMem { gpu, p })
+    }
+
+    fn from_slice<T: Copy>(gpu: &'a Gpu, src: &[T]) -> io::Result<Self> {
+        let bytes = std::mem::size_of_val(src);
+        let m = Self::alloc(gpu, bytes.max(1))?;
+        let ctx = gpu.ctx();
+        let stream = unsafe { sys::sdgpu_stream(*ctx) };
+        check(unsafe { sys::sdgpu_memcpy_async(*ctx, m.p, src.as_ptr().cast(), bytes, stream) })?;
+        // the source slice may go away before the copy runs
+        check(unsafe { sys::sdgpu_sync(*ctx) })?;
+        Ok(m)
+    }
+
+    fn ptr(&self) -> *mut std::os::raw::c_void {
+        self.p
+    }
+
+    fn read_into<T: Copy>(&self, gpu: &Gpu, dst: &mut [T]) -> io::Result<()> {
+        let ctx = gpu.ctx();
+        let stream = unsafe { sys::sdgpu_stream(*ctx) };
+        check(unsafe {
+            sys::sdgpu_memcpy_async(*ctx, dst.as_mut_ptr().cast(), self.p, std::mem::size_of_val(dst),
+                                    stream)
+        })?;
+        check(unsafe { sys::sdgpu_sync(*ctx) })
+    }
+
+    fn read_u32(&self, gpu: &Gpu) -> io::Result<u32> {
+        let mut v = [0u32; 1];
+        self.read_into(gpu, &mut v)?;
+        Ok(v[0])
+    }
+}
+
+impl Drop for DeviceMem<'_> {
+    fn drop(&mut self) {
+        // the calls above end with sdgpu_sync: nothing still reads the buffer
+        unsafe { sys::sdgpu_free_device(*self.gpu.ctx(), self.p) };
+    }
 }
 
 /// What one batched read + hash of the candidates gives (FileMetadata::new of

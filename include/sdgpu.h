@@ -235,7 +235,7 @@ typedef struct sdgpu_index sdgpu_index;
 int sdgpu_index_create(sdgpu_ctx *ctx, uint64_t capacity_hint, sdgpu_index **out);
 int sdgpu_index_destroy(sdgpu_index *idx);
 int sdgpu_index_clear(sdgpu_index *idx, void *stream);
-/* Distinct keys stored (synchronises). */
+/* Distinct keys stored: live keys, removed ones not counted (synchronises). */
 int sdgpu_index_count(sdgpu_index *idx, uint64_t *count);
 /* Register pre-existing Objects: d_key[i] -> SDGPU_REP_EXISTING | d_handle[i].
  * Only keys whose shard belongs to `rank` of `world` are kept (world = 1: all),
@@ -244,6 +244,69 @@ int sdgpu_index_count(sdgpu_index *idx, uint64_t *count);
 int sdgpu_index_add_objects_device(sdgpu_index *idx, const uint64_t *d_key,
                                    const uint32_t *d_handle, uint64_t n, uint32_t world,
                                    uint32_t rank, void *stream);
+
+/* ---- a library-lifetime index (ABI 6, additive) -------------------------------
+ * An index that outlives one identifier job has to follow what the reference
+ * does to Objects behind the identifier's back: the orphan remover deletes
+ * Objects by id (core/src/object/orphan_remover.rs:57-90), the watcher's
+ * delete / update paths delete an Object left without file_paths
+ * (location/manager/watcher/utils.rs:746-765) and its create path asks "does
+ * an Object own this cas_id" for one file (utils.rs:240-275).  The calls
+ * below answer and maintain that; a grouping through the index afterwards
+ * treats a removed key as one the library-wide find_many no longer returns
+ * (its next row creates an Object again).
+ * A removed entry keeps its slot until the table is next rebuilt (growth
+ * drops removed slots and sizes the new table from the live keys, so
+ * capacity stays bounded under churn); inserting the key again revives it.
+ * LIMIT: the index keeps ONE Object per key, the lowest registered handle.
+ * When that Object is removed while another Object still owns the same
+ * cas_id, the index forgets the key: the caller re-registers the survivor
+ * with sdgpu_index_add_objects_device (it has it: the reference's own query
+ * for such Objects is mod.rs:168-175).
+ * Sharded index (add_objects with world > 1): every rank's share may be given
+ * the same key / handle lists; keys of other shards are simply absent. */
+/* (ABI 6, additive) sdgpu_index_lookup's value for a key the index does not hold. */
+#define SDGPU_INDEX_MISS 0xFFFFFFFFu
+/* (ABI 6, additive) d_value[i] = the stored value of d_key[i], exactly as a
+ * grouping's rep would show it (a row rank, or SDGPU_REP_EXISTING | handle),
+ * SDGPU_INDEX_MISS when the key is absent or removed.  A pure read: does not
+ * grow the table, does not synchronise.  A share of a sharded index misses
+ * the keys of the other shards: the caller takes the non-miss answer across
+ * the shares. */
+int sdgpu_index_lookup_device(sdgpu_index *idx, const uint64_t *d_key, uint64_t n,
+                              uint32_t *d_value, void *stream);
+/* (ABI 6, additive) The same on host arrays (the watcher's single-file case):
+ * copy in, one launch, copy out; returns when done. */
+int sdgpu_index_lookup(sdgpu_index *idx, const uint64_t *key, uint64_t n, uint32_t *value);
+/* (ABI 6, additive) Removes d_key[0..n).  d_value (may be NULL): key i is
+ * removed only while its stored value equals d_value[i] (an Object that took
+ * the key over since the caller looked is left alone).  d_removed (device
+ * uint32_t, may be NULL) receives the number of keys actually removed: a key
+ * listed several times counts once, an absent key not at all. */
+int sdgpu_index_remove_device(sdgpu_index *idx, const uint64_t *d_key, const uint32_t *d_value,
+                              uint64_t n, uint32_t *d_removed, void *stream);
+/* (ABI 6, additive) Removes every entry whose value is SDGPU_REP_EXISTING | h
+ * for an h in d_handle[0..n) -- the orphan remover's shape: it knows Object
+ * ids, not cas_ids.  The ids sdgpu_orphan_objects_device writes are usable
+ * directly as d_handle (negative ids and ids above max_handle match nothing);
+ * max_handle < 2^31 sizes the mark map (max_handle + 1 bytes of the context's
+ * workspace, as sdgpu_orphan_objects_device).  One pass over the slots;
+ * entries holding row ranks are never touched.  d_removed as above. */
+int sdgpu_index_remove_objects_device(sdgpu_index *idx, const int32_t *d_handle, uint64_t n,
+                                      uint32_t max_handle, uint32_t *d_removed, void *stream);
+/* (ABI 6, additive) The live entries as dense (key, value) arrays of at most
+ * cap pairs, in no particular order (compare as a set), the key ~0 included;
+ * values as sdgpu_index_lookup_device shows them.  d_count[0] (device) = the
+ * number of live entries: when it exceeds cap nothing was written past cap
+ * and the caller retries with larger arrays.  To load a saved index:
+ * sdgpu_index_add_objects_device for the SDGPU_REP_EXISTING entries (rank
+ * entries belong to the run that made them). */
+int sdgpu_index_export_device(sdgpu_index *idx, uint64_t *d_key, uint32_t *d_value, uint64_t cap,
+                              uint32_t *d_count, void *stream);
+/* (ABI 6, additive) out = {live keys, slots in use including removed ones,
+ * capacity in slots} (synchronises, like sdgpu_index_count). */
+int sdgpu_index_stats(sdgpu_index *idx, uint64_t out[3]);
+
 /* sdgpu_group_rows_device against the index: a keyed row whose key is in the
  * index gets rep = the index value if it is an existing Object, else (a rank
  * f of an earlier batch) rep = r when r and f share a chunk and f otherwise;

@@ -19,6 +19,8 @@ _lib = None
 c_u8p = ctypes.c_void_p
 c_vp = ctypes.c_void_p
 
+INDEX_MISS = 0xFFFFFFFF  # include/sdgpu.h SDGPU_INDEX_MISS
+
 
 class SdgpuError(OSError):
     """A negative errno returned by libsdgpu (maps to Rust's io::Error)."""
@@ -77,6 +79,12 @@ def _proto(L):
         "sdgpu_index_clear": (i32, [c_vp, c_vp]),
         "sdgpu_index_count": (i32, [c_vp, P(ctypes.c_uint64)]),
         "sdgpu_index_add_objects_device": (i32, [c_vp, c_vp, c_vp, u64, u32, u32, c_vp]),
+        "sdgpu_index_lookup_device": (i32, [c_vp, c_vp, u64, c_vp, c_vp]),
+        "sdgpu_index_lookup": (i32, [c_vp, c_vp, u64, c_vp]),
+        "sdgpu_index_remove_device": (i32, [c_vp, c_vp, c_vp, u64, c_vp, c_vp]),
+        "sdgpu_index_remove_objects_device": (i32, [c_vp, c_vp, u64, u32, c_vp, c_vp]),
+        "sdgpu_index_export_device": (i32, [c_vp, c_vp, c_vp, u64, c_vp, c_vp]),
+        "sdgpu_index_stats": (i32, [c_vp, P(ctypes.c_uint64)]),
         "sdgpu_group_rows_indexed_device": (i32, [ctx, c_vp, c_vp, c_vp, c_vp, u64, u32, c_vp,
                                                   c_vp]),
         "sdgpu_dedup_batch": (i32, [ctx, c_vp, c_vp, c_vp, u32, u32, u32, c_vp]),

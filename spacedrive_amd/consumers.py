@@ -39,6 +39,23 @@ def orphan_objects(object_ids, fp_object_ids, max_object_id: int, ctx=None, trim
     return out[:int(cnt.item())]
 
 
+def remove_orphans_from_index(index, object_ids, fp_object_ids, max_object_id: int,
+                              count: bool = True):
+    """The orphan remover's deletions applied to a library-lifetime Object
+    index: orphan_objects(...) on the device, its result handed straight to
+    ObjectIndex.remove_objects -- no host round trip in between (the full-length
+    list's tail past the orphan count is masked to -1 on the device, which
+    matches no entry).  Returns (orphans, count, removed): the full-length
+    int32 list, its device count [1], and the number of index entries removed
+    (an int; the device tensor with count=False, no synchronisation)."""
+    import torch
+    out, cnt = orphan_objects(object_ids, fp_object_ids, max_object_id, index.ctx, trim=False)
+    pos = torch.arange(out.numel(), dtype=torch.int32, device=out.device)
+    out = torch.where(pos < cnt, out, torch.full_like(out, -1))
+    removed = index.remove_objects(out, max_object_id, count=count)
+    return out, cnt, removed
+
+
 def thumbnail_shards(cas8, valid=None, ctx=None, trim: bool = True):
     """(order, counts): rows with a cas_id ordered by thumbnail directory
     (stable inside a directory), and rows per directory (256).  trim=False:

@@ -285,11 +285,15 @@ hipError_t scatter_rep_launch(const uint32_t* src, const uint32_t* pos, uint64_t
 // rep values with this bit name a pre-existing Object handle, not a row rank.
 constexpr uint32_t kRepExisting = 0x80000000u;
 struct IndexRef {
-  uint4* slots = nullptr;              // [cap] {key lo, key hi, value, 0}
+  uint4* slots = nullptr;              // [cap] {key lo, key hi, value, removed flag}
   uint64_t cap = 0;                    // power of two
-  unsigned long long* count = nullptr; // distinct keys stored (device)
-  uint32_t* special = nullptr;         // [2]: key ~0 present, its value
+  unsigned long long* count = nullptr; // slots in use, removed ones included (device)
+  uint32_t* special = nullptr;         // [2]: key ~0 has its slot, its value (slot encoding)
+  unsigned long long* dead = nullptr;  // removed slots still in the table (device):
+                                       // live keys = count - dead; key ~0 in neither
 };
+// sdgpu_index_lookup's answer for a key the index does not hold.
+constexpr uint32_t kIndexMiss = 0xFFFFFFFFu;
 hipError_t index_clear_launch(const IndexRef& t, hipStream_t s);
 hipError_t index_rehash_launch(const IndexRef& from, const IndexRef& to, hipStream_t s);
 hipError_t index_objects_launch(const IndexRef& t, const uint64_t* key, const uint32_t* handle,
@@ -304,6 +308,23 @@ hipError_t index_probe_launch(const IndexRef& t, const GroupInput& in, uint32_t 
 hipError_t index_creators_launch(const IndexRef& t, const GroupInput& in, const uint32_t* rep,
                                  const uint8_t* grouped, hipStream_t s, KTimer* timer = nullptr,
                                  const uint32_t* skip = nullptr);
+// value[i] = stored value of key[i] or kIndexMiss; a pure read.
+hipError_t index_lookup_launch(const IndexRef& t, const uint64_t* key, uint64_t n,
+                               uint32_t* value, hipStream_t s, KTimer* timer = nullptr);
+// value (may be null): remove key[i] only while it holds value[i].  removed
+// (device, may be null) = keys actually removed.
+hipError_t index_remove_launch(const IndexRef& t, const uint64_t* key, const uint32_t* value,
+                               uint64_t n, uint32_t* removed, hipStream_t s,
+                               KTimer* timer = nullptr);
+// Entries whose value is EXISTING | h for an h of handle[0..n): ws holds
+// index_mark_workspace_bytes(max_handle) bytes (cleared by the call).
+size_t index_mark_workspace_bytes(uint32_t max_handle);
+hipError_t index_remove_objects_launch(const IndexRef& t, const int32_t* handle, uint64_t n,
+                                       uint32_t max_handle, uint32_t* removed, void* ws,
+                                       hipStream_t s, KTimer* timer = nullptr);
+// Live entries as dense arrays of at most cap_out pairs; d_count = all of them.
+hipError_t index_export_launch(const IndexRef& t, uint64_t* key, uint32_t* value, uint64_t cap_out,
+                               uint32_t* d_count, hipStream_t s, KTimer* timer = nullptr);
 
 // ---- downstream consumers (consumers.hip) ---------------------------------------
 size_t orphan_workspace_bytes(uint64_t n_obj, uint32_t max_id);

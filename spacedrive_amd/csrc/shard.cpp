@@ -174,9 +174,9 @@ struct sdgpu_comm {
 
 struct sdgpu_index {
   sdgpu_ctx* ctx = nullptr;
-  DevBuf buf;       // [slots cap*16 | count 8 | special 8]
+  DevBuf buf;       // [slots cap*16 | count 8 | special 8 | dead 8 | pad 8]
   IndexRef ref;
-  uint64_t ub = 0;  // host upper bound of the stored key count
+  uint64_t ub = 0;  // host upper bound of the slots in use
 };
 
 namespace {
@@ -291,7 +291,7 @@ int stream_wait(sdgpu_comm* m, hipStream_t s, Clock::time_point deadline) {
 // ---- Object index ------------------------------------------------------------
 
 int index_alloc(sdgpu_ctx* c, DevBuf& b, uint64_t cap, IndexRef& r) {
-  const size_t bytes = 16 * cap + 16;
+  const size_t bytes = 16 * cap + 32;
   void* p = nullptr;
   SD_TRY(hipMalloc(&p, bytes));
   b.p = p;
@@ -300,6 +300,7 @@ int index_alloc(sdgpu_ctx* c, DevBuf& b, uint64_t cap, IndexRef& r) {
   r.cap = cap;
   r.count = reinterpret_cast<unsigned long long*>(static_cast<uint8_t*>(p) + 16 * cap);
   r.special = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(p) + 16 * cap + 8);
+  r.dead = reinterpret_cast<unsigned long long*>(static_cast<uint8_t*>(p) + 16 * cap + 16);
   (void)c;
   return 0;
 }
@@ -310,27 +311,48 @@ uint64_t pow2_at_least(uint64_t x) {
   return p;
 }
 
-// Make room for `add` more keys at load <= 1/2.  The exact count is read (one
+// Make room for `add` more keys at load <= 1/2.  The exact counts are read (one
 // synchronisation of s) only when the host-side upper bound says it may not fit.
+// Slots in use (removed ones included: they still lengthen probe chains)
+// decide WHEN the table is rebuilt; the live keys decide its new size, since
+// the rehash drops removed slots -- a table worn out by removals is rebuilt
+// at the same capacity or a smaller one, not doubled.
 int index_reserve(sdgpu_index* x, uint64_t add, hipStream_t s) {
   if (x->ub + add <= x->ref.cap / 2) {
     x->ub += add;
     return 0;
   }
-  unsigned long long cnt = 0;
-  SD_TRY(hipMemcpyAsync(&cnt, x->ref.count, 8, hipMemcpyDeviceToHost, s));
+  unsigned long long used = 0, dead = 0;
+  SD_TRY(hipMemcpyAsync(&used, x->ref.count, 8, hipMemcpyDeviceToHost, s));
+  SD_TRY(hipMemcpyAsync(&dead, x->ref.dead, 8, hipMemcpyDeviceToHost, s));
   SD_TRY(hipStreamSynchronize(s));
-  if (cnt + add > x->ref.cap / 2) {
+  const unsigned long long live = used - dead;
+  if (used + add > x->ref.cap / 2) {
     DevBuf nb;
     IndexRef nr;
-    SD_TRY_RC(index_alloc(x->ctx, nb, pow2_at_least(4 * (cnt + add)), nr));
+    SD_TRY_RC(index_alloc(x->ctx, nb, pow2_at_least(4 * (live + add)), nr));
     SD_TRY(index_rehash_launch(x->ref, nr, s));
     SD_TRY(hipStreamSynchronize(s));
     (void)hipFree(x->buf.p);
     x->buf = nb;
     x->ref = nr;
+    used = live;
   }
-  x->ub = cnt + add;
+  x->ub = used + add;
+  return 0;
+}
+
+// {live keys, slots in use, capacity}, the key ~0 included (synchronises s).
+int index_read_stats(sdgpu_index* x, hipStream_t s, uint64_t out[3]) {
+  unsigned long long used = 0, dead = 0;
+  uint32_t sp[2] = {0, 0};
+  SD_TRY(hipMemcpyAsync(&used, x->ref.count, 8, hipMemcpyDeviceToHost, s));
+  SD_TRY(hipMemcpyAsync(&dead, x->ref.dead, 8, hipMemcpyDeviceToHost, s));
+  SD_TRY(hipMemcpyAsync(sp, x->ref.special, 8, hipMemcpyDeviceToHost, s));
+  SD_TRY(hipStreamSynchronize(s));
+  out[0] = used - dead + (sp[0] && sp[1] != 0xFFFFFFFFu ? 1 : 0);  // special: has a value
+  out[1] = used + (sp[0] ? 1 : 0);
+  out[2] = x->ref.cap;
   return 0;
 }
 
@@ -1436,12 +1458,79 @@ int sdgpu_index_count(sdgpu_index* x, uint64_t* count) {
   std::lock_guard<std::mutex> g(x->ctx->mu);
   SD_TRY(hipSetDevice(x->ctx->device));
   hipStream_t s = pick(x->ctx, nullptr);
-  unsigned long long cnt = 0;
-  uint32_t sp[2] = {0, 0};
-  SD_TRY(hipMemcpyAsync(&cnt, x->ref.count, 8, hipMemcpyDeviceToHost, s));
-  SD_TRY(hipMemcpyAsync(sp, x->ref.special, 8, hipMemcpyDeviceToHost, s));
+  uint64_t st[3];
+  SD_TRY_RC(index_read_stats(x, s, st));
+  *count = st[0];
+  return 0;
+}
+
+int sdgpu_index_stats(sdgpu_index* x, uint64_t out[3]) {
+  if (!x || !out) return -EINVAL;
+  std::lock_guard<std::mutex> g(x->ctx->mu);
+  SD_TRY(hipSetDevice(x->ctx->device));
+  return index_read_stats(x, pick(x->ctx, nullptr), out);
+}
+
+int sdgpu_index_lookup_device(sdgpu_index* x, const uint64_t* d_key, uint64_t n, uint32_t* d_value,
+                              void* stream) {
+  if (!x || (n && (!d_key || !d_value))) return -EINVAL;
+  std::lock_guard<std::mutex> g(x->ctx->mu);
+  SD_TRY(hipSetDevice(x->ctx->device));
+  hipStream_t s = pick(x->ctx, stream);
+  SD_TRY(index_lookup_launch(x->ref, d_key, n, d_value, s, x->ctx->kt()));
+  return 0;
+}
+
+int sdgpu_index_lookup(sdgpu_index* x, const uint64_t* key, uint64_t n, uint32_t* value) {
+  if (!x || (n && (!key || !value))) return -EINVAL;
+  if (n == 0) return 0;
+  sdgpu_ctx* c = x->ctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  SD_TRY(hipSetDevice(c->device));
+  hipStream_t s = pick(c, nullptr);
+  // keys [n] | values [n] in the context's link workspace (grow-only: the
+  // watcher's single-key calls allocate nothing after the first)
+  const size_t o_val = align_up(8 * n, 256);
+  SD_TRY_RC(ensure_dev(c, c->link_ws, o_val + 4 * n));
+  uint64_t* dk = static_cast<uint64_t*>(c->link_ws.p);
+  uint32_t* dv = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(c->link_ws.p) + o_val);
+  SD_TRY(hipMemcpyAsync(dk, key, 8 * n, hipMemcpyHostToDevice, s));
+  SD_TRY(index_lookup_launch(x->ref, dk, n, dv, s, c->kt()));
+  SD_TRY(hipMemcpyAsync(value, dv, 4 * n, hipMemcpyDeviceToHost, s));
   SD_TRY(hipStreamSynchronize(s));
-  *count = cnt + (sp[0] ? 1 : 0);
+  return 0;
+}
+
+int sdgpu_index_remove_device(sdgpu_index* x, const uint64_t* d_key, const uint32_t* d_value,
+                              uint64_t n, uint32_t* d_removed, void* stream) {
+  if (!x || (n && !d_key)) return -EINVAL;
+  std::lock_guard<std::mutex> g(x->ctx->mu);
+  SD_TRY(hipSetDevice(x->ctx->device));
+  hipStream_t s = pick(x->ctx, stream);
+  SD_TRY(index_remove_launch(x->ref, d_key, d_value, n, d_removed, s, x->ctx->kt()));
+  return 0;
+}
+
+int sdgpu_index_remove_objects_device(sdgpu_index* x, const int32_t* d_handle, uint64_t n,
+                                      uint32_t max_handle, uint32_t* d_removed, void* stream) {
+  if (!x || (n && !d_handle) || max_handle >= kRepExisting) return -EINVAL;
+  sdgpu_ctx* c = x->ctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  SD_TRY(hipSetDevice(c->device));
+  hipStream_t s = pick(c, stream);
+  if (n) SD_TRY_RC(ensure_dev(c, c->link_ws, index_mark_workspace_bytes(max_handle)));
+  SD_TRY(index_remove_objects_launch(x->ref, d_handle, n, max_handle, d_removed, c->link_ws.p, s,
+                                     c->kt()));
+  return 0;
+}
+
+int sdgpu_index_export_device(sdgpu_index* x, uint64_t* d_key, uint32_t* d_value, uint64_t cap,
+                              uint32_t* d_count, void* stream) {
+  if (!x || !d_count || (cap && (!d_key || !d_value))) return -EINVAL;
+  std::lock_guard<std::mutex> g(x->ctx->mu);
+  SD_TRY(hipSetDevice(x->ctx->device));
+  hipStream_t s = pick(x->ctx, stream);
+  SD_TRY(index_export_launch(x->ref, d_key, d_value, cap, d_count, s, x->ctx->kt()));
   return 0;
 }
 

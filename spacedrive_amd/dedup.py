@@ -243,6 +243,84 @@ class ObjectIndex:
             self.h, key.data_ptr(), handle.data_ptr(), key.numel(), world, rank, s),
             "sdgpu_index_add_objects_device")
 
+    # ---- a library-lifetime index (include/sdgpu.h, "ABI 6, additive") ---------
+    def lookup(self, key):
+        """Stored value per key (a rank, or REP_EXISTING | handle), INDEX_MISS
+        for absent or removed keys.  A device int64 tensor gives a device int32
+        tensor (sdgpu_index_lookup_device: no synchronisation); an int or a
+        numpy / sequence of u64 keys goes through the host form
+        (sdgpu_index_lookup) and gives an int or a uint32 array."""
+        try:
+            import torch
+            is_tensor = isinstance(key, torch.Tensor)
+        except ImportError:
+            is_tensor = False
+        if is_tensor:
+            value = torch.empty(key.numel(), dtype=torch.int32, device=key.device)
+            s = torch.cuda.current_stream(key.device).cuda_stream
+            check(self.ctx.lib.sdgpu_index_lookup_device(
+                self.h, key.data_ptr(), key.numel(), value.data_ptr(), s),
+                "sdgpu_index_lookup_device")
+            return value
+        scalar = np.isscalar(key)
+        k = np.ascontiguousarray(np.atleast_1d(np.asarray(key, np.uint64)))
+        value = np.zeros(k.size, np.uint32)
+        check(self.ctx.lib.sdgpu_index_lookup(self.h, k.ctypes.data, k.size, value.ctypes.data),
+              "sdgpu_index_lookup")
+        return int(value[0]) if scalar else value
+
+    def remove(self, key, value=None, count: bool = True):
+        """Removes the keys (device int64 tensor); with `value` (device int32:
+        what lookup returned) a key goes only while it still holds that value.
+        Returns the number of keys actually removed (one host read), or the
+        device count tensor with count=False (no synchronisation)."""
+        import torch
+        removed = torch.empty(1, dtype=torch.int32, device=key.device)
+        s = torch.cuda.current_stream(key.device).cuda_stream
+        check(self.ctx.lib.sdgpu_index_remove_device(
+            self.h, key.data_ptr(), value.data_ptr() if value is not None else None, key.numel(),
+            removed.data_ptr(), s), "sdgpu_index_remove_device")
+        return int(removed.item()) if count else removed
+
+    def remove_objects(self, handles, max_handle: int, count: bool = True):
+        """Removes every entry REP_EXISTING | h for h in `handles` (device
+        int32 Object ids, e.g. consumers.orphan_objects' result; negative ids
+        and ids above max_handle match nothing).  Returns as remove()."""
+        import torch
+        removed = torch.empty(1, dtype=torch.int32, device=handles.device)
+        s = torch.cuda.current_stream(handles.device).cuda_stream
+        check(self.ctx.lib.sdgpu_index_remove_objects_device(
+            self.h, handles.data_ptr(), handles.numel(), max_handle, removed.data_ptr(), s),
+            "sdgpu_index_remove_objects_device")
+        return int(removed.item()) if count else removed
+
+    def export(self, cap: int | None = None):
+        """(key int64, value int32) device tensors of the live entries, in no
+        particular order, trimmed to their count; one retry with the reported
+        count when `cap` (default: count()) was too small."""
+        import torch
+        dev = torch.device("cuda", self.ctx.device)
+        s = torch.cuda.current_stream(dev).cuda_stream
+        cap = self.count() if cap is None else int(cap)
+        for _ in range(2):
+            key = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+            value = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+            cnt = torch.empty(1, dtype=torch.int32, device=dev)
+            check(self.ctx.lib.sdgpu_index_export_device(
+                self.h, key.data_ptr(), value.data_ptr(), cap, cnt.data_ptr(), s),
+                "sdgpu_index_export_device")
+            n = int(cnt.item()) & 0xFFFFFFFF
+            if n <= cap:
+                return key[:n], value[:n]
+            cap = n
+        raise RuntimeError("index changed while it was exported")
+
+    def stats(self) -> tuple:
+        """(live keys, slots in use including removed ones, capacity in slots)."""
+        out = (ctypes.c_uint64 * 3)()
+        check(self.ctx.lib.sdgpu_index_stats(self.h, out), "sdgpu_index_stats")
+        return int(out[0]), int(out[1]), int(out[2])
+
 
 def group_rows_indexed(key, has_key, rank, index: ObjectIndex, chunk_rows: int = CHUNK_SIZE):
     """rep (int32, device) of one batch of rows against `index`, which then

@@ -278,11 +278,20 @@ class FileIdentifierJob:
     library's existing Objects and this run's creators -- so the Objects are
     the reference's whatever the step size.  state() / resume() persist the
     cursor and counters (the JobState of job/mod.rs:701-720); a resumed job
-    re-registers the Objects already in the table."""
+    re-registers the Objects already in the table.
+
+    index: an optional caller-owned ObjectIndex that outlives the job (a
+    library-lifetime index, include/sdgpu.h).  The job then neither reloads
+    the library's existing Objects into it nor closes it; the caller keeps it
+    true to the table between jobs (ObjectIndex.remove / remove_objects when
+    Objects are deleted).  Row ranks mean nothing to the next job, so after
+    every step the Objects the step created are registered under their Object
+    ids (add_objects: a registered Object supersedes the rank entry; steps are
+    whole chunks, so later rows link to the same Objects either way)."""
 
     def __init__(self, table: FilePaths, location_id: int, location_path: str,
                  sub_path: str | None = None, chunks_per_step: int = 64, ctx=None,
-                 _shallow_dir: str | None = None):
+                 _shallow_dir: str | None = None, index=None):
         self.table = table
         self.location_id = location_id
         self.location_path = location_path
@@ -298,7 +307,8 @@ class FileIdentifierJob:
         self.step_number = 0      # reference steps (chunks of 100) done
         self.task_count = 0
         self._creator_object: dict[int, int] = {}  # rank -> Object id (this run)
-        self.index = None
+        self.index = index
+        self._owns_index = index is None
 
     # ---- reference: init (file_identifier_job.rs:80-172) -------------------------
     def init(self) -> "FileIdentifierJob":
@@ -319,6 +329,8 @@ class FileIdentifierJob:
         """The library's existing Objects into the device index, page by page
         (the index grows as it fills)."""
         import torch
+        if not self._owns_index:
+            return  # the caller's index already holds the library's Objects
         self.index = _dedup.ObjectIndex(self.ctx, max(1024, 2 * self.meta.total_orphan_paths))
         dev = torch.device("cuda", self.ctx.device)
         after = None
@@ -376,6 +388,7 @@ class FileIdentifierJob:
             key[j] = keys8[i]
         rep = _dedup.dedup_batch(key, has, first_rank, self.index, CHUNK_SIZE, self.ctx)
         created = linked = 0
+        new_keys, new_objs = [], []  # this step's keyed creators (caller-owned index)
         t = self.table
         for j, f in enumerate(rows):  # the write set, in rank order (mod.rs:144-333)
             if not valid[j]:
@@ -388,6 +401,9 @@ class FileIdentifierJob:
                 t.next_object_id += 1
                 self._creator_object[r] = obj
                 created += 1
+                if has[j]:
+                    new_keys.append(key[j])
+                    new_objs.append(obj)
             elif rep[j] & _dedup.REP_EXISTING:
                 obj = int(rep[j] & 0x7FFFFFFF)
                 linked += 1
@@ -395,6 +411,12 @@ class FileIdentifierJob:
                 obj = self._creator_object[int(rep[j])]
                 linked += 1
             t.object_id[i] = obj
+        if not self._owns_index and new_keys:
+            import torch
+            dev = torch.device("cuda", self.ctx.device)
+            self.index.add_objects(
+                torch.from_numpy(np.asarray(new_keys, np.uint64).view(np.int64)).to(dev),
+                torch.from_numpy(np.asarray(new_objs, np.int32)).to(dev))
         self.step_number += len(fetched)
         self.meta.cursor = cursor
         self.meta.total_objects_created += created
@@ -418,9 +440,9 @@ class FileIdentifierJob:
                 "task_count": self.task_count, "run_metadata": asdict(self.meta)}
 
     @classmethod
-    def resume(cls, table: FilePaths, state: dict, ctx=None) -> "FileIdentifierJob":
+    def resume(cls, table: FilePaths, state: dict, ctx=None, index=None) -> "FileIdentifierJob":
         job = cls(table, state["location_id"], state["location_path"], state["sub_path"],
-                  state["chunks_per_step"], ctx, state.get("shallow_dir"))
+                  state["chunks_per_step"], ctx, state.get("shallow_dir"), index=index)
         job.meta = IdentifierRunMetadata(**state["run_metadata"])
         job.step_number = state["step_number"]
         job.task_count = state["task_count"]
@@ -428,9 +450,9 @@ class FileIdentifierJob:
         return job
 
     def close(self):
-        if self.index is not None:
+        if self.index is not None and self._owns_index:
             self.index.close()
-            self.index = None
+        self.index = None
 
 
 class EarlyFinish(Exception):
