@@ -139,7 +139,10 @@ hipError_t synth_dedup_rows_launch(uint64_t seed, uint64_t total_rows, uint64_t 
                                    uint64_t first_rank, uint64_t n, uint64_t* key,
                                    uint8_t* has_key, uint32_t* rank, hipStream_t s);
 
-// ---- dedup (K4-K6) ------------------------------------------------------------
+// ---- dedup (K4-K6, dedup.hip) ---------------------------------------------------
+// Multi-GPU shards: h >> 56 (256 shards; rank d owns shards s with s*W>>8 == d);
+// the grouping's bucket digits are the hash bits below.
+constexpr uint32_t kShardBits = 8;
 // Rows of one grouping call: either the caller's arrays (key[i], valid[i]
 // (null: all keyed), rank[i] (null: rank_base + i)) or packed 12-byte exchange
 // records {key lo, key hi, rank} (rec12, all keyed unless valid is given).
@@ -161,7 +164,7 @@ size_t dedup_workspace_bytes(uint64_t n, bool with_sink = false);
 // get rep = their rank when init_rep, and are left untouched otherwise).
 hipError_t dedup_local_launch(const GroupInput& in, uint32_t chunk_rows, uint32_t* rep,
                               bool init_rep, void* ws, hipStream_t s, KTimer* timer = nullptr);
-// The grouping as the Object write set (ListOut in dedup.hip): per bucket, in
+// The grouping as the Object write set (ListOut in group_device.hpp): per bucket, in
 // its record range, creators from the front (who = rank) and linked rows from
 // the back (who = rank | SDGPU_LINKED, obj = creator rank); no rep array.
 // counts[0..2] (zeroed by the caller) += creators, linked; counts[2] = keyed
@@ -170,7 +173,7 @@ hipError_t dedup_local_launch(const GroupInput& in, uint32_t chunk_rows, uint32_
 // null: all) as creators behind the keyed entries -- what extra_list_launch
 // does without an index, with no pass of its own.
 // The valid keyless rows of a write set collected by a partition pass into
-// per-wave segments (dedup.hip XSink): kPartBlocks x 16 segments of cap rows
+// per-wave segments (part_device.hpp sink_keyless): kPartBlocks x 16 segments of cap rows
 // (keyless_sink_cap of the partitioned rows), their counts in cnt.
 struct KeylessSink {
   const uint8_t* valid = nullptr;  // null: every keyless row is valid
@@ -200,7 +203,8 @@ hipError_t extra_list_launch(const uint8_t* has, const uint8_t* valid, const uin
                              uint64_t n, uint32_t* who, uint32_t* obj, uint32_t* counts, void* ws,
                              hipStream_t s, KTimer* timer = nullptr, uint32_t cap = 0xFFFFFFFFu,
                              uint32_t* nospc = nullptr);
-// Compact return leg of the exchange (dedup.hip): the received rows are cut
+// ---- device steps of the multi-GPU exchange (exchange.hip) ------------------------
+// Compact return leg of the exchange: the received rows are cut
 // into tiles of 4096 that never straddle a source's segment [roff[p],
 // roff[p + 1]); tstart[p] = first tile of segment p, tstart[world] = tiles.
 constexpr uint32_t kMaxWorld = 64;
@@ -257,7 +261,7 @@ hipError_t gather_rep_launch(const uint32_t* back, const uint32_t* pos, const ui
                              uint64_t n, uint32_t* rep, hipStream_t s, const uint32_t* self = nullptr,
                              uint64_t self_lo = 0, uint64_t self_hi = 0);
 // Padded exchange (fixed-capacity messages of cap + 1 12-byte slots per
-// destination rank, dedup.hip k_part_padded / k_pad_fill): one pass writes
+// destination rank, k_part_padded / k_pad_fill): one pass writes
 // the keyed rows into their owners' messages -- the message to rank `me`
 // into self_rec12 (the receive buffer), the others into rec12 -- reserving
 // slots through cursor[world] (device u32, zero on entry); out_pos (may be

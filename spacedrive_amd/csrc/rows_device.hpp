@@ -1,5 +1,5 @@
-// Device-side row access shared by the grouping (dedup.hip) and the Object
-// index (index.hip): the key hash and the two row layouts the kernels read.
+// Device-side row access shared by the grouping (dedup.hip), the exchange and
+// the Object index (index.hip): the key hash and the row layouts the kernels read.
 #pragma once
 
 #include <hip/hip_runtime.h>

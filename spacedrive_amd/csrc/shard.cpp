@@ -181,8 +181,6 @@ struct sdgpu_index {
 
 namespace {
 
-constexpr uint32_t kXShardBits = 8;  // 256 shards; rank d owns shards s with s*W>>8 == d
-
 // SDGPU_RETURN_AUTO: the compact return leg saves 2.4 B per returned row on
 // every link (8-B pairs for the ~20 % linked rows instead of 4 B for all) but
 // costs a second count exchange + host synchronisation and three kernels:
@@ -596,7 +594,7 @@ int exchange_forward(std::vector<RankJob>& J, int W, Clock::time_point t_start,
     const size_t o_rpcnt = align_up(o_pcnt + 8ull * W, 256);
     const size_t o_summ = align_up(o_rpcnt + 8ull * W, 256);
     SD_TRY_RC(ensure_dev(j.c, j.c->xs_send, o_summ + 32));
-    SD_TRY_RC(ensure_dev(j.c, j.c->shard_ws, shard_workspace_bytes(kXShardBits)));
+    SD_TRY_RC(ensure_dev(j.c, j.c->shard_ws, shard_workspace_bytes(kShardBits)));
     SD_TRY_RC(ensure_pin(j.c->xs_counts, 64ull * W));
     uint8_t* b = static_cast<uint8_t*>(j.c->xs_send.p);
     j.srec = reinterpret_cast<uint32_t*>(b);
@@ -643,7 +641,7 @@ int exchange_forward(std::vector<RankJob>& J, int W, Clock::time_point t_start,
       c->xs_cursor_clean = true;
       c->xs_parity ^= 1u;
     } else {
-      SD_TRY(shard_exchange_launch(j.key, j.has, j.rank, n, kXShardBits, W, nullptr, nullptr,
+      SD_TRY(shard_exchange_launch(j.key, j.has, j.rank, n, kShardBits, W, nullptr, nullptr,
                                    j.srec, list ? nullptr : j.spos, j.dcnt, j.c->shard_ws.p, j.s,
                                    j.c->kt(), j.xmsg, code));
     }

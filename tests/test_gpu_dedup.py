@@ -16,11 +16,19 @@ def test_golden_grouping_fixture(ctx):
     np.testing.assert_array_equal(rep, z["rep"])
 
 
+# Row counts at which the partition path changes (csrc/dedup.hip group_layout:
+# kBucketRows = 3072 rows per bucket, kStageBits = 12): the last direct and the
+# first 12-bit staged call, the last 12-bit staged and the first two-level one.
+PATH_EDGES = [3073 * 2**11 - 1, 3073 * 2**11, 3073 * 2**12 - 1, 3073 * 2**12]
+
+
 @pytest.mark.parametrize("n,pool", [(0, 1), (1, 1), (2, 1), (1000, 10), (200_000, 150_000),
-                                    (1_000_000, 900_000), (300_000, 1), (500_000, 7)])
+                                    (1_000_000, 900_000), (300_000, 1), (500_000, 7)] +
+                         [(n, n * 4 // 5) for n in PATH_EDGES])
 def test_random_vs_oracle(ctx, n, pool):
     """Includes buckets far beyond the LDS table (one key 300k times: the
-    global-table path) and a sentinel-valued key."""
+    global-table path), a sentinel-valued key, and the row counts on either
+    side of a change of partition path."""
     from spacedrive_amd import dedup
     rng = np.random.default_rng(n + pool)
     keys = rng.integers(0, 2**64 - 1, max(pool, 1), dtype=np.uint64, endpoint=True)
@@ -283,10 +291,12 @@ def test_two_level_fine_count_overflow(ctx):
     np.testing.assert_array_equal(dedup.group_reps(key2, has, 100, ctx), O.group_reps(key2, has, 100))
 
 
-@pytest.mark.parametrize("n,chunk", [(12_500_000, 100), (7_000_000, 7), (13_000_000, 100)])
+@pytest.mark.parametrize("n,chunk", [(12_500_000, 100), (7_000_000, 7), (13_000_000, 100)] +
+                         [(n, 100) for n in PATH_EDGES])
 def test_implicit_rank_12_byte_records(ctx, n, chunk):
     """Rows without a rank array (rank = row): the 12-bit and the two-level
-    (13 M rows) paths move 12-byte records {hash, row}.  Same reps as with the explicit rank array (16-byte
+    (13 M rows) paths move 12-byte records {hash, row}; PATH_EDGES: either
+    side of each change of path, for both record sizes.  Same reps as with the explicit rank array (16-byte
     records) and as the oracle; sentinel-valued keys and keyless rows included."""
     import torch
     from spacedrive_amd import dedup

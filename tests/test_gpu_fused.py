@@ -252,8 +252,8 @@ def test_fused_every_row_decided_by_the_index(ctx):
 
 @pytest.mark.parametrize("n", [300_001, 7_000_001])
 def test_fused_keyless_sink_on_unaligned_rows(ctx, n):
-    """The keyless rows are collected by the first partition pass (XSink in
-    dedup.hip).  Key / has_key / valid views that start one row into their
+    """The keyless rows are collected by the first partition pass (sink_keyless in
+    part_device.hpp).  Key / has_key / valid views that start one row into their
     buffers miss the histogram's paired 16-B / 2-B loads, so the per-row
     path collects them (small-table and 12-bit paths); the aligned case runs
     in the other tests."""

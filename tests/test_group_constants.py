@@ -1,5 +1,5 @@
 """The group kernels' open-addressing invariants, read from the kernel source
-(csrc/dedup.hip): every double-hashing step must be coprime with its table's
+(csrc/group_device.hpp): every double-hashing step must be coprime with its table's
 slot count, or a probe sequence cycles through a subset of the slots and a
 full enough bucket never finds a free one (the kernel's probe loop has no
 other exit).  CPU-only: it checks the constants, the GPU tests check the
@@ -9,7 +9,7 @@ import os
 import re
 
 SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
-                   "spacedrive_amd", "csrc", "dedup.hip")
+                   "spacedrive_amd", "csrc", "group_device.hpp")
 
 
 def _const(text, name):
