@@ -46,6 +46,9 @@
 //               million times) is handled.
 // Kernels: part_device.hpp (shared with the exchange), bucket_part_device.hpp
 // (K6), group_device.hpp (K5).  Here: the layout, the path choice, the entries.
+#include <cerrno>
+#include <cstdlib>
+
 #include "bucket_part_device.hpp"
 #include "group_device.hpp"
 #include "scan_device.hpp"
@@ -80,7 +83,37 @@ constexpr uint32_t kStage2Coarse = kPartBlocks / kStage2Blocks;  // per second-p
 // one pass scatters at most 2^12 digits: its cursors fit the default dynamic LDS
 static_assert((sizeof(uint32_t) << kStageBits) <= (64u << 10), "no hipFuncSetAttribute needed");
 
+// TEST-ONLY overrides of the plan, read once per process like SDGPU_POISON_WS
+// (ctx.hpp): the path of a call depends on its row count alone, so without
+// them a test reaches a path only by being big enough for it -- the histogram
+// one never (tests/test_gpu_forced_paths.py).  No benchmark and no default
+// sets them; unset, group_layout decides as it always did.
+//   SDGPU_GROUP_BITS=<1..kMaxBucketBits>  the bucket bits of every grouping
+//       call of the process, bits_rows hint or not (other values: ignored);
+//   SDGPU_GROUP_HIST=1  a two-level call takes Path::kTwoLevelHist whatever
+//       its round count.
+struct ForcedPlan {
+  uint32_t bits = 0;  // 0: bucket_bits_for decides
+  bool hist = false;
+};
+const ForcedPlan& forced_plan() {
+  static const ForcedPlan f = [] {
+    ForcedPlan p;
+    if (const char* b = std::getenv("SDGPU_GROUP_BITS")) {
+      char* end = nullptr;
+      const long v = std::strtol(b, &end, 10);
+      if (end != b && *end == 0 && v >= 1 && v <= static_cast<long>(kMaxBucketBits))
+        p.bits = static_cast<uint32_t>(v);
+    }
+    const char* h = std::getenv("SDGPU_GROUP_HIST");
+    p.hist = h && h[0] == '1' && h[1] == 0;
+    return p;
+  }();
+  return f;
+}
+
 // A call's path and its workspace as typed arrays (ws null: only `total`).
+constexpr uint32_t kLayoutArrays = 18;  // = the take() calls of group_layout
 struct GroupLayout {
   Path path;
   bool rec12;  // 12-byte bucket records (rank_in_z); the direct path has 16-byte ones only
@@ -95,6 +128,10 @@ struct GroupLayout {
   uint32_t* lcnt;        // ListOut: linked rows per bucket, keyed total
   uint32_t *xst, *xcnt;  // ListOut's keyless sink (KeylessSink)
   size_t total;
+  // every array above in workspace order, as bytes (sdgpu_group_plan)
+  struct Span {
+    uint64_t off, bytes;
+  } span[kLayoutArrays];
 };
 
 // bits_rows (0: n): the rows the buckets are sized for -- the keyed rows of a
@@ -107,7 +144,8 @@ struct GroupLayout {
 GroupLayout group_layout(uint64_t n, uint64_t bits_rows, bool with_sink, bool z_rank,
                          void* ws = nullptr) {
   GroupLayout L;
-  L.bits = bucket_bits_for(bits_rows && bits_rows < n ? bits_rows : n);
+  const ForcedPlan& forced = forced_plan();  // tests only
+  L.bits = forced.bits ? forced.bits : bucket_bits_for(bits_rows && bits_rows < n ? bits_rows : n);
   L.cbits = L.bits > kStageBits ? L.bits - kStage2Bits : 0;
   L.rec12 = z_rank && L.bits >= kStageBits;
   // rounds in the largest coarse tile (kPartBlocks tiles); the run table is
@@ -116,18 +154,21 @@ GroupLayout group_layout(uint64_t n, uint64_t bits_rows, bool with_sink, bool z_
   const auto rounds = [&](uint32_t r) { return static_cast<uint32_t>((tile + r - 1) / r); };
   const uint32_t table_rounds = rounds(priv_round<false>());
   L.rounds = L.rec12 ? rounds(priv_round<true>()) : table_rounds;
-  L.path = L.bits < kStageBits                    ? Path::kDirect
-           : !L.cbits                             ? Path::kStaged12
-           : kStage2Coarse * L.rounds <= kMaxRuns ? Path::kTwoLevelRuns
-                                                  : Path::kTwoLevelHist;
+  const bool runs_fit = kStage2Coarse * static_cast<uint64_t>(L.rounds) <= kMaxRuns;
+  L.path = L.bits < kStageBits         ? Path::kDirect
+           : !L.cbits                  ? Path::kStaged12
+           : runs_fit && !forced.hist  ? Path::kTwoLevelRuns
+                                       : Path::kTwoLevelHist;
   const uint64_t nh = (static_cast<uint64_t>(1) << L.bits) * kMaxPartBlocks;
   const uint64_t nh1 = (static_cast<uint64_t>(1) << L.cbits) * kMaxPartBlocks;
   const uint64_t nf = static_cast<uint64_t>(1) << L.bits;
   const uint64_t nrun = static_cast<uint64_t>(kPartBlocks) * table_rounds * kRunMaxBins;
   const uint64_t nsink = with_sink ? static_cast<uint64_t>(kPartBlocks) * kSinkWaves : 0;
   size_t o = 0;
+  uint32_t na = 0;
   const auto take = [&](auto*& p, uint64_t bytes) {  // the next 256-B aligned bytes
     p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(reinterpret_cast<uintptr_t>(ws) + o);
+    L.span[na++] = {o, bytes};
     o = align_up(o + bytes, 256);
   };
   take(L.hist, 4 * (nh + 1));
@@ -359,7 +400,8 @@ hipError_t two_level_runs_launch(const GroupCall<In, Out>& c) {
 // The two-level partition when a block's coarse rounds outgrow the second
 // pass's run list (kMaxRuns): a histogram pass and a scan give the coarse
 // pass global offsets, and the staged scatter reads whole segments.  Only
-// above ~2^28 rows per call; no test reaches it.
+// above ~2^28 rows per call; tests/test_gpu_forced_paths.py reaches it at small
+// row counts through SDGPU_GROUP_HIST (forced_plan).
 template <bool kRec12, typename In, typename Out>
 hipError_t two_level_hist_launch(const GroupCall<In, Out>& c) {
   using RecT = typename std::conditional<kRec12, uint3, uint4>::type;
@@ -465,3 +507,26 @@ hipError_t dedup_list_launch(const GroupInput& in, uint32_t chunk_rows, uint32_t
 }
 
 }  // namespace sdgpu
+
+// The plan of a grouping call -- what group_layout decides from the row count
+// (and the test-only overrides), without touching a device: for tests
+// (internal.hpp; not part of the C ABI of include/sdgpu.h).
+extern "C" int sdgpu_group_plan(uint64_t n, uint64_t bits_rows, int implicit_rank, int with_sink,
+                                uint64_t* out, uint32_t cap) {
+  using namespace sdgpu;
+  constexpr uint32_t kHead = 7, kWords = kHead + 2 * kLayoutArrays;
+  if (!out || cap < kWords || n == 0) return -EINVAL;
+  const GroupLayout L = group_layout(n, bits_rows, with_sink != 0, implicit_rank != 0);
+  out[0] = L.bits;
+  out[1] = L.cbits;
+  out[2] = L.rec12;
+  out[3] = L.rounds;  // as passed to the two-level kernels
+  out[4] = static_cast<uint64_t>(L.path);
+  out[5] = L.total;
+  out[6] = dedup_workspace_bytes(n, with_sink != 0);  // what a caller allocates for n rows
+  for (uint32_t a = 0; a < kLayoutArrays; ++a) {  // GroupLayout's arrays in workspace order
+    out[kHead + 2 * a] = L.span[a].off;
+    out[kHead + 1 + 2 * a] = L.span[a].bytes;
+  }
+  return static_cast<int>(kWords);
+}

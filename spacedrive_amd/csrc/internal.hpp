@@ -349,3 +349,16 @@ hipError_t link_batch_launch(const uint32_t* rep, const uint32_t* rank, const ui
                              KTimer* timer = nullptr);
 
 }  // namespace sdgpu
+
+// ---- test hook (dedup.hip): NOT part of the C ABI of include/sdgpu.h ----------------
+// The plan group_layout makes for a grouping call of n rows (bits_rows: the
+// hint of a padded receive, 0: none; implicit_rank: rows without a rank array
+// or RecRankIn records; with_sink: the fused call's keyless sink), computed on
+// the host alone.  out[0..7): bits, cbits, rec12, rounds, path (0 direct, 1
+// staged 12-bit, 2 two-level runs, 3 two-level histogram), total bytes,
+// dedup_workspace_bytes(n, with_sink); then (byte offset, byte size) of every
+// workspace array in GroupLayout's order: hist, tiles, rec, hist1, rec1, gkey,
+// gmin, fine, fE, ftot, fbase, ovf, run_s, run_l, segtot, lcnt, xst, xcnt.
+// Returns the words written (43), or -EINVAL (n == 0, out null, cap too small).
+extern "C" int sdgpu_group_plan(uint64_t n, uint64_t bits_rows, int implicit_rank, int with_sink,
+                                uint64_t* out, uint32_t cap);
