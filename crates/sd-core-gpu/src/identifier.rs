@@ -258,6 +258,50 @@ pub fn identify(gpu: &Gpu, paths: &[PathBuf], sizes: Option<&[u64]>) -> io::Resu
     Ok(out)
 }
 
+/// `identify` plus the integrity_checksum of every file it read whole, from
+/// the same read (`sdgpu_identify_checksum_files`): `has_checksum[i]` is 1 for
+/// a row with status 0 whose size is in (0, 100 KiB], and `checksum32[i]` is
+/// then BLAKE3 of the bytes that went into its cas_id -- what `file_checksum`
+/// (validation/hash.rs:10-24) would have returned at that moment.  The object
+/// validator's query (validator_job.rs:100-116: integrity_checksum NULL) then
+/// returns only the sampled and the empty files.
+pub struct IdentifiedWithChecksums {
+    pub rows: Identified,
+    pub checksum32: Vec<[u8; 32]>,
+    pub has_checksum: Vec<u8>,
+}
+
+impl IdentifiedWithChecksums {
+    /// The `integrity_checksum` column value of row i (64 hex chars), if any.
+    pub fn integrity_checksum(&self, i: usize) -> Option<String> {
+        (self.has_checksum[i] != 0).then(|| hex::encode(self.checksum32[i]))
+    }
+}
+
+pub fn identify_with_checksums(gpu: &Gpu, paths: &[PathBuf], sizes: Option<&[u64]>)
+                               -> io::Result<IdentifiedWithChecksums> {
+    let n = paths.len();
+    if sizes.map_or(false, |s| s.len() != n) {
+        return Err(io::Error::new(io::ErrorKind::InvalidInput, "one size per path"));
+    }
+    let c: Vec<_> = paths.iter().map(|p| cpath(p)).collect();
+    let ptrs: Vec<*const c_char> = c.iter().map(|s| s.as_ptr()).collect();
+    let mut out = IdentifiedWithChecksums {
+        rows: Identified { cas8: vec![[0u8; 8]; n], has_key: vec![0u8; n], status: vec![0i32; n] },
+        checksum32: vec![[0u8; 32]; n],
+        has_checksum: vec![0u8; n],
+    };
+    let ctx = gpu.ctx();
+    check(unsafe {
+        sys::sdgpu_identify_checksum_files(*ctx, ptrs.as_ptr(),
+                                           sizes.map_or(std::ptr::null(), |s| s.as_ptr()), n as u32,
+                                           out.rows.cas8.as_mut_ptr(), out.rows.has_key.as_mut_ptr(),
+                                           out.checksum32.as_mut_ptr(), out.has_checksum.as_mut_ptr(),
+                                           out.rows.status.as_mut_ptr())
+    })?;
+    Ok(out)
+}
+
 /// The grouping of one batch of identified rows against the index (rows in
 /// id order, ranks first_rank + i); rows whose read failed take no part.
 pub fn group(gpu: &Gpu, idx: &ObjectIndex<'_>, rows: &Identified, first_rank: u32) -> io::Result<Vec<IdentifiedRow>> {

@@ -97,6 +97,22 @@ int sdgpu_cas_batch(sdgpu_ctx *ctx, const uint8_t *msg_arena, const uint64_t *ms
 int sdgpu_cas_batch_device(sdgpu_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes,
                            const uint64_t *d_off, const uint32_t *d_len, uint32_t n,
                            uint8_t *d_out8, int32_t *d_status, void *stream);
+/* (ABI 6, additive) sdgpu_cas_batch_device plus the integrity_checksum of the
+ * files read whole: d_out8 and d_status are exactly what sdgpu_cas_batch_device
+ * gives for the same arguments.  d_whole is device u8[n]: message i with
+ * d_whole[i] != 0 is u64 size LE || a whole file (cas.rs:27-29), and for every
+ * such message with status 0 and len >= 8, d_out32[i] (device [n][32], 4-B
+ * aligned) = BLAKE3(arena[off + 8 .. off + len)) -- file_checksum of those
+ * bytes (hash.rs:10-24) -- and d_has_checksum[i] (device u8[n]) = 1.  Every
+ * other message gets 32 zero bytes and d_has_checksum 0; under -ENOBUFS that
+ * is every message.  The digests come from a second K1 pass over the message
+ * bodies on the same stream; no byte at or beyond off + len is read.  NULL
+ * d_whole, d_out32 or d_has_checksum with n > 0 is -EINVAL. */
+int sdgpu_cas_checksum_batch_device(sdgpu_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes,
+                                    const uint64_t *d_off, const uint32_t *d_len,
+                                    const uint8_t *d_whole, uint32_t n, uint8_t *d_out8,
+                                    uint8_t *d_out32, uint8_t *d_has_checksum, int32_t *d_status,
+                                    void *stream);
 
 /* Pinned-host staged variant (the identifier's "pinned async staging", BASELINE
  * config 5): the messages live in caller-owned PINNED host memory (e.g. where
@@ -127,6 +143,20 @@ int sdgpu_generate_cas_id(sdgpu_ctx *ctx, const char *path, uint64_t size, char 
  * -EISDIR (the reference asserts the path is not one, mod.rs:69-72). */
 int sdgpu_identify_files(sdgpu_ctx *ctx, const char *const *paths, const uint64_t *size,
                          uint32_t n, uint8_t (*out8)[8], uint8_t *has_key, int32_t *status);
+/* (ABI 6, additive) sdgpu_identify_files that also returns the
+ * integrity_checksum of every file it read whole, from the same read: out8,
+ * has_key and status are exactly what sdgpu_identify_files gives.
+ * has_checksum[i] = 1 iff status[i] is 0 and the size used (the one passed, or
+ * the one stat-ed when size is NULL) is in (0, 100 KiB]; out32[i] is then
+ * BLAKE3 of the bytes the call read -- the bytes that went into the cas_id,
+ * what file_checksum(path) (hash.rs:10-24) would have returned at that moment,
+ * also for a file that grew since its size was taken.  Every other row (size
+ * 0: not opened; sampled files; failed rows) gets has_checksum 0 and 32 zero
+ * bytes, and is left to the object validator (sdgpu_checksum_files).  out32
+ * and has_checksum must not be NULL when n > 0. */
+int sdgpu_identify_checksum_files(sdgpu_ctx *ctx, const char *const *paths, const uint64_t *size,
+                                  uint32_t n, uint8_t (*out8)[8], uint8_t *has_key,
+                                  uint8_t (*out32)[32], uint8_t *has_checksum, int32_t *status);
 
 /* ---- K2/K3: full-file checksum -------------------------------------------------
  * Replaces file_checksum (core/src/object/validation/hash.rs:10-24). */

@@ -50,6 +50,8 @@ def _proto(L):
         "sdgpu_memcpy_async": (i32, [ctx, c_vp, c_vp, sz, c_vp]),
         "sdgpu_cas_batch": (i32, [ctx, c_vp, c_vp, c_vp, u32, c_vp, c_vp]),
         "sdgpu_cas_batch_device": (i32, [ctx, c_vp, u64, c_vp, c_vp, u32, c_vp, c_vp, c_vp]),
+        "sdgpu_cas_checksum_batch_device": (i32, [ctx, c_vp, u64, c_vp, c_vp, c_vp, u32, c_vp, c_vp,
+                                                  c_vp, c_vp, c_vp]),
         "sdgpu_cas_stage_pinned": (i32, [ctx, c_vp, c_vp, c_vp, u32, c_vp, c_vp, c_vp]),
         "sdgpu_link_batch_device": (i32, [ctx, c_vp, c_vp, c_vp, u32, u64, c_vp, c_vp, c_vp, c_vp,
                                           c_vp]),
@@ -57,6 +59,7 @@ def _proto(L):
                                           c_vp, c_vp, c_vp]),
         "sdgpu_generate_cas_id": (i32, [ctx, ctypes.c_char_p, u64, ctypes.c_char_p]),
         "sdgpu_identify_files": (i32, [ctx, c_vp, c_vp, u32, c_vp, c_vp, c_vp]),
+        "sdgpu_identify_checksum_files": (i32, [ctx, c_vp, c_vp, u32, c_vp, c_vp, c_vp, c_vp, c_vp]),
         "sdgpu_checksum": (i32, [ctx, c_vp, u64, c_vp]),
         "sdgpu_checksum_batch_device": (i32, [ctx, c_vp, c_vp, u32, c_vp, c_vp]),
         "sdgpu_subtree_device": (i32, [ctx, c_vp, u64, u64, i32, c_vp, c_vp]),

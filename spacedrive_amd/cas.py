@@ -88,6 +88,35 @@ def cas_batch_device(arena, off, length, out=None, status=None, ctx=None, stream
     return out, status
 
 
+def cas_checksum_batch_device(arena, off, length, whole, out=None, out32=None, has_checksum=None,
+                              status=None, ctx=None, stream=None):
+    """K1 plus its body pass over device tensors: ``cas_batch_device`` that also
+    returns the integrity_checksum of the messages flagged in `whole` (uint8,
+    1 = the message is size_le || a whole file): BLAKE3 of the message without
+    its 8-byte prefix (sdgpu_cas_checksum_batch_device).
+
+    Returns (out[n,8] uint8, out32[n,32] uint8, has_checksum[n] uint8,
+    status[n] int32) on the same device; asynchronous on `stream`."""
+    import torch
+    ctx = ctx or default_context(arena.device.index)
+    n = off.numel()
+    dev = arena.device
+    if out is None:
+        out = torch.empty((n, 8), dtype=torch.uint8, device=dev)
+    if out32 is None:
+        out32 = torch.empty((n, 32), dtype=torch.uint8, device=dev)
+    if has_checksum is None:
+        has_checksum = torch.empty(n, dtype=torch.uint8, device=dev)
+    if status is None:
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+    s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    check(ctx.lib.sdgpu_cas_checksum_batch_device(
+        ctx.h, arena.data_ptr(), arena.numel(), off.data_ptr(), length.data_ptr(),
+        whole.data_ptr(), n, out.data_ptr(), out32.data_ptr(), has_checksum.data_ptr(),
+        status.data_ptr(), s), "sdgpu_cas_checksum_batch_device")
+    return out, out32, has_checksum, status
+
+
 def cas_stage_pinned(h_arena, off, length, out=None, status=None, ctx=None, device=None,
                      stream=None):
     """K1 over messages in PINNED host memory (torch pinned uint8 tensor), in

@@ -37,6 +37,20 @@
 // arena).  A message that ends past the arena is -EINVAL; if the messages
 // overlap so much that U + n exceeds the capacity, every message gets -ENOBUFS
 // and nothing is written past the workspace.
+//
+// Body pass (kSkip == 8, integrity_checksum of the files read whole): the same
+// four kernels over the BODY of every message flagged `whole`, M_i[8, len_i) --
+// the file's bytes without the size prefix, a BLAKE3 input of its own whose
+// chunk 0 starts at off_i + 8, with 8 digest words out.  It runs after the cas
+// pass on the same stream and reuses its workspace; units_of(len - 8) <=
+// units_of(len), so the capacity that held the cas pass holds it.  The body is
+// 8-byte aligned, never 16: its blocks are loaded with 8-byte loads
+// (b3_load_block<8>, b3_chunk_full<8>; the compiler pairs them into dwordx4 at
+// 8-byte alignment), which cover exactly the block they load.  A full block [p, p + 64) ends at or before off_i + len_i and a ragged
+// last block goes through b3_load_block_partial, so no load of the pass
+// touches a byte at or beyond off_i + len_i, also for a body whose length is a
+// multiple of 1024 (or of 64) at the very end of the arena -- where dwordx4
+// loads from the 16-byte aligned p - 8 would read 8 bytes too far.
 #include <errno.h>
 #include <stdlib.h>
 
@@ -153,6 +167,40 @@ __device__ __forceinline__ bool msg_ok(uint64_t o, uint32_t l, uint32_t max_len,
   return l <= max_len && (o & 15u) == 0 && o <= arena_bytes && l <= arena_bytes - o;
 }
 
+// What a pass hashes of message i: hl bytes from off[i] + kSkip.  The cas pass
+// (kSkip == 0) hashes every valid message; the body pass (kSkip == 8) the
+// valid messages flagged in `whole` that hold the 8-byte prefix.  The loads of
+// a pass are aligned to kAlignOf<kSkip>.
+template <uint32_t kSkip>
+constexpr uint32_t kAlignOf = kSkip ? 8u : 16u;
+
+template <uint32_t kSkip>
+__device__ __forceinline__ bool pass_msg(uint64_t o, uint32_t l, const uint8_t* __restrict__ whole,
+                                         uint32_t i, uint32_t max_len, uint64_t arena_bytes,
+                                         uint32_t& hl) {
+  static_assert(kSkip == 0 || kSkip == 8, "the cas message or its body");
+  bool ok = msg_ok(o, l, max_len, arena_bytes);
+  hl = l;
+  if constexpr (kSkip != 0) {
+    ok = ok && l >= kSkip && whole[i] != 0;
+    hl = l - kSkip;
+  }
+  return ok;
+}
+
+// The CV slots of the batch (U + n) exceed the workspace: nothing is hashed.
+// The body pass runs in the cas pass's workspace and follows its decision,
+// which its plan kernel left in grab[1] (the body's own U is never larger).
+template <uint32_t kSkip>
+__device__ __forceinline__ bool over_capacity(const uint32_t* d_units, uint32_t n, uint64_t cap,
+                                              const uint32_t* grab) {
+  if constexpr (kSkip != 0) return grab[1] != 0;
+  return static_cast<uint64_t>(*d_units) + n > cap;
+}
+
+// `whole`, `has`, `cap`: the body pass only (has[i] = 1 for the messages it hashes;
+// *d_units is still the cas pass's unit count here, the scan comes after).
+template <uint32_t kSkip>
 __global__ __launch_bounds__(kThreads) void k_plan3(const uint64_t* __restrict__ off,
                                                     const uint32_t* __restrict__ len, uint32_t n,
                                                     uint32_t max_len, uint64_t arena_bytes,
@@ -160,17 +208,24 @@ __global__ __launch_bounds__(kThreads) void k_plan3(const uint64_t* __restrict__
                                                     uint32_t* __restrict__ hist,
                                                     uint32_t* __restrict__ grab,
                                                     int32_t* __restrict__ status,
-                                                    uint32_t out_words, uint32_t* __restrict__ out) {
+                                                    uint32_t out_words, uint32_t* __restrict__ out,
+                                                    const uint8_t* __restrict__ whole,
+                                                    uint8_t* __restrict__ has,
+                                                    const uint32_t* d_units, uint64_t cap) {
   __shared__ uint32_t h[2][kBins];
   for (uint32_t t = threadIdx.x; t < 2 * kBins; t += kThreads) (&h[0][0])[t] = 0;
-  if (blockIdx.x == 0 && threadIdx.x == 0) *grab = 0;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    *grab = 0;
+    if constexpr (kSkip != 0) grab[1] = over_capacity<0>(d_units, n, cap, nullptr) ? 1u : 0u;
+  }
   __syncthreads();
   const Range3 r = block_range3(n);
   for (uint32_t i = r.lo + threadIdx.x; i < r.hi; i += kThreads) {
-    const uint32_t l = len[i];
-    const bool ok = msg_ok(off[i], l, max_len, arena_bytes);
+    uint32_t l;
+    const bool ok = pass_msg<kSkip>(off[i], len[i], whole, i, max_len, arena_bytes, l);
     units[i] = ok ? units_of(l) : 0u;
     if (status) status[i] = ok ? 0 : -EINVAL;
+    if constexpr (kSkip != 0) has[i] = ok ? 1 : 0;
     if (!ok)
       for (uint32_t w = 0; w < out_words; ++w) out[i * out_words + w] = 0u;
     uint32_t b0, b1;
@@ -183,14 +238,10 @@ __global__ __launch_bounds__(kThreads) void k_plan3(const uint64_t* __restrict__
     hist[static_cast<size_t>(t) * gridDim.x + blockIdx.x] = (&h[0][0])[t];
 }
 
-// The CV slots of the batch (U + n) exceed the workspace: nothing is hashed.
-__device__ __forceinline__ bool over_capacity(const uint32_t* d_units, uint32_t n, uint64_t cap) {
-  return static_cast<uint64_t>(*d_units) + n > cap;
-}
-
 // Scatter both lane orders (positions from the scanned histograms: key 0 lands
 // in [0, R), key 1 in [R, R + F)) and fill the unit -> message map.  Over
 // capacity, every message is marked -ENOBUFS instead.
+template <uint32_t kSkip>
 __global__ __launch_bounds__(kThreads) void k_scatter3(const uint64_t* __restrict__ off,
                                                        const uint32_t* __restrict__ len, uint32_t n,
                                                        uint32_t max_len, uint64_t arena_bytes,
@@ -200,12 +251,16 @@ __global__ __launch_bounds__(kThreads) void k_scatter3(const uint64_t* __restric
                                                        const uint32_t* __restrict__ unit_base,
                                                        const uint32_t* __restrict__ hist_scan,
                                                        uint32_t* __restrict__ order,
-                                                       uint32_t* __restrict__ unit_msg) {
+                                                       uint32_t* __restrict__ unit_msg,
+                                                       const uint8_t* __restrict__ whole,
+                                                       uint8_t* __restrict__ has,
+                                                       const uint32_t* __restrict__ grab) {
   __shared__ uint32_t cur[2][kBins], cnt[2][kBins];
   const Range3 r = block_range3(n);
-  if (over_capacity(d_units, n, cap)) {  // uniform over the grid
+  if (over_capacity<kSkip>(d_units, n, cap, grab)) {  // uniform over the grid
     for (uint32_t i = r.lo + threadIdx.x; i < r.hi; i += kThreads) {
       if (status) status[i] = -ENOBUFS;
+      if constexpr (kSkip != 0) has[i] = 0;
       for (uint32_t w = 0; w < out_words; ++w) out[i * out_words + w] = 0u;
     }
     return;
@@ -219,8 +274,8 @@ __global__ __launch_bounds__(kThreads) void k_scatter3(const uint64_t* __restric
     const uint32_t i = i0 + threadIdx.x;
     uint32_t b0 = kBins, b1 = kBins, l0 = 0, l1 = 0;
     if (i < r.hi) {
-      const uint32_t l = len[i];
-      const bool ok = msg_ok(off[i], l, max_len, arena_bytes);
+      uint32_t l;
+      const bool ok = pass_msg<kSkip>(off[i], len[i], whole, i, max_len, arena_bytes, l);
       bins3(l, ok, b0, b1);
       if (b0 < kBins) l0 = atomicAdd(&cnt[0][b0], 1u);
       if (b1 < kBins) l1 = atomicAdd(&cnt[1][b1], 1u);
@@ -241,6 +296,7 @@ __global__ __launch_bounds__(kThreads) void k_scatter3(const uint64_t* __restric
 }
 
 // One 4-chunk unit: level-2 node of chunks [4g, 4g + 4) of message m.
+template <uint32_t kSkip>
 __device__ __forceinline__ void unit_item(const uint8_t* __restrict__ arena,
                                           const uint64_t* __restrict__ off,
                                           const uint32_t* __restrict__ unit_msg,
@@ -250,55 +306,59 @@ __device__ __forceinline__ void unit_item(const uint8_t* __restrict__ arena,
   const uint32_t ub = unit_base[m];
   const uint32_t g = u - ub;
   const uint32_t j0 = 4 * g;
-  const uint8_t* p = arena + off[m] + static_cast<uint64_t>(j0) * B3_CHUNK_LEN;
+  const uint8_t* p = arena + off[m] + kSkip + static_cast<uint64_t>(j0) * B3_CHUNK_LEN;
+  constexpr uint32_t kA = kAlignOf<kSkip>;
   uint32_t a[8], b[8], c[8];
-  b3_chunk_full(p, j0, a);
-  b3_chunk_full(p + 1024, j0 + 1, b);
+  b3_chunk_full<kA>(p, j0, a);
+  b3_chunk_full<kA>(p + 1024, j0 + 1, b);
   b3_parent(a, a, b, 0u);
-  b3_chunk_full(p + 2048, j0 + 2, b);
-  b3_chunk_full(p + 3072, j0 + 3, c);
+  b3_chunk_full<kA>(p + 2048, j0 + 2, b);
+  b3_chunk_full<kA>(p + 3072, j0 + 3, c);
   b3_parent(b, b, c, 0u);
   b3_parent(c, a, b, 0u);
   store_cv(cvs + static_cast<uint64_t>(ub + m + g) * 8, c);
 }
 
 // Chunk j of a message (full chunks take the 128-byte-line path).
+template <uint32_t kAlign>
 __device__ __forceinline__ void chunk_any(const uint8_t* __restrict__ p, uint32_t l, uint32_t j,
                                           uint32_t root_flag, uint32_t cv[8]) {
   const uint32_t clen = min(B3_CHUNK_LEN, l - j * B3_CHUNK_LEN);
   const uint8_t* cp = p + static_cast<uint64_t>(j) * B3_CHUNK_LEN;
   if (clen == B3_CHUNK_LEN && root_flag == 0)
-    b3_chunk_full(cp, j, cv);
+    b3_chunk_full<kAlign>(cp, j, cv);
   else
-    b3_chunk(cp, clen, j, root_flag, cv);
+    b3_chunk<kAlign>(cp, clen, j, root_flag, cv);
 }
 
 // Message item: the node of chunks [4q, nch) (the whole message, with ROOT,
 // when q == 0).  1..4 chunks form the left-complete subtree
 // c0 | P(c0,c1) | P(P(c0,c1),c2) | P(P(c0,c1),P(c2,c3)), built with the
 // same three CV registers as a unit.
+template <uint32_t kSkip>
 __device__ __forceinline__ void msg_item(const uint8_t* __restrict__ arena,
                                          const uint64_t* __restrict__ off,
                                          const uint32_t* __restrict__ len,
                                          const uint32_t* __restrict__ unit_base, uint32_t m,
                                          uint32_t* __restrict__ cvs, uint32_t out_words,
                                          uint32_t* __restrict__ out) {
-  const uint32_t l = len[m];
+  const uint32_t l = len[m] - kSkip;
   const uint32_t nch = n_chunks_of(l), q = units_of(l);
   const uint32_t rem = nch - 4 * q;  // 1..4
-  const uint8_t* p = arena + off[m];
+  const uint8_t* p = arena + off[m] + kSkip;
   const uint32_t rootf = q == 0 ? B3_ROOT : 0u;
   const uint32_t j0 = 4 * q;
+  constexpr uint32_t kA = kAlignOf<kSkip>;
   uint32_t a[8], b[8], c[8];
-  chunk_any(p, l, j0, rem == 1 ? rootf : 0u, a);
+  chunk_any<kA>(p, l, j0, rem == 1 ? rootf : 0u, a);
   if (rem >= 2) {
-    chunk_any(p, l, j0 + 1, 0u, b);
+    chunk_any<kA>(p, l, j0 + 1, 0u, b);
     b3_parent(a, a, b, rem == 2 ? rootf : 0u);
   }
   if (rem >= 3) {
-    chunk_any(p, l, j0 + 2, 0u, b);
+    chunk_any<kA>(p, l, j0 + 2, 0u, b);
     if (rem == 4) {
-      chunk_any(p, l, j0 + 3, 0u, c);
+      chunk_any<kA>(p, l, j0 + 3, 0u, c);
       b3_parent(b, b, c, 0u);
     }
     b3_parent(a, a, b, rootf);
@@ -314,6 +374,7 @@ __device__ __forceinline__ void msg_item(const uint8_t* __restrict__ arena,
 // of spill and measured no faster.
 constexpr int kLeavesMinBlocks = 5;
 
+template <uint32_t kSkip>
 __global__ __launch_bounds__(kThreads, kLeavesMinBlocks) void k_leaves3(
     const uint8_t* __restrict__ arena, const uint64_t* __restrict__ off,
     const uint32_t* __restrict__ len, const uint32_t* __restrict__ unit_msg,
@@ -321,7 +382,7 @@ __global__ __launch_bounds__(kThreads, kLeavesMinBlocks) void k_leaves3(
     const uint32_t* __restrict__ order, const uint32_t* __restrict__ d_r,
     uint32_t* __restrict__ grab, uint32_t* __restrict__ cvs, uint32_t out_words,
     uint32_t* __restrict__ out, uint32_t n, uint64_t cap) {
-  if (over_capacity(d_units, n, cap)) return;
+  if (over_capacity<kSkip>(d_units, n, cap, grab)) return;
   const uint32_t U = *d_units;
   const uint32_t total = U + *d_r;
   const uint32_t lane = threadIdx.x & 63u;
@@ -332,9 +393,9 @@ __global__ __launch_bounds__(kThreads, kLeavesMinBlocks) void k_leaves3(
     if (base >= total) break;  // uniform: every wave reaches this exit
     const uint32_t i = base + lane;
     if (i < U)
-      unit_item(arena, off, unit_msg, unit_base, i, cvs);
+      unit_item<kSkip>(arena, off, unit_msg, unit_base, i, cvs);
     else if (i < total)
-      msg_item(arena, off, len, unit_base, order[i - U], cvs, out_words, out);
+      msg_item<kSkip>(arena, off, len, unit_base, order[i - U], cvs, out_words, out);
   }
 }
 
@@ -343,6 +404,7 @@ __global__ __launch_bounds__(kThreads, kLeavesMinBlocks) void k_leaves3(
 // staged messages fall back to the in-place pairwise fold.
 constexpr uint32_t kFoldStack = 5;
 
+template <uint32_t kSkip>
 __global__ __launch_bounds__(kThreads) void k_fold3(const uint32_t* __restrict__ len,
                                                     const uint32_t* __restrict__ unit_base,
                                                     const uint32_t* __restrict__ order,
@@ -351,14 +413,15 @@ __global__ __launch_bounds__(kThreads) void k_fold3(const uint32_t* __restrict__
                                                     uint32_t* __restrict__ cvs, uint32_t out_words,
                                                     uint32_t* __restrict__ out,
                                                     const uint32_t* __restrict__ d_units, uint32_t n,
-                                                    uint64_t cap) {
+                                                    uint64_t cap,
+                                                    const uint32_t* __restrict__ grab) {
   __shared__ uint32_t stk[kFoldStack][8][kThreads];
-  if (over_capacity(d_units, n, cap)) return;
+  if (over_capacity<kSkip>(d_units, n, cap, grab)) return;
   const uint32_t R = *d_r;
   const uint32_t i = R + blockIdx.x * kThreads + threadIdx.x;
   if (i >= *d_end) return;
   const uint32_t m = order[i];
-  const uint32_t l = len[m];
+  const uint32_t l = len[m] - kSkip;
   const uint32_t q = units_of(l);
   const uint32_t cnt = q + (n_chunks_of(l) > 4 * q ? 1u : 0u);
   uint32_t* c = cvs + static_cast<uint64_t>(unit_base[m] + m) * 8;
@@ -404,7 +467,11 @@ uint32_t leaves3_grid() {
   if (dev != cached_dev) {
     int cus = 0, per = 0;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_leaves3, kThreads, 0);
+    // the cas and the body instantiation may differ by a few registers
+    int per_body = 0;
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_leaves3<0>, kThreads, 0);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_body, k_leaves3<8>, kThreads, 0);
+    per = std::min(per, per_body);
     cached = static_cast<uint32_t>(std::max(1, cus) * std::max(1, per));
     cached_dev = dev;
   }
@@ -820,36 +887,58 @@ __global__ __launch_bounds__(kSvcThreads) void k_service(SvcMailbox* mb, uint8_t
 
 }  // namespace
 
-hipError_t batch_hash_launch(const uint8_t* arena, uint64_t arena_bytes, const uint64_t* off,
-                             const uint32_t* len, uint32_t n, uint32_t max_len,
-                             uint32_t out_words, uint8_t* out, int32_t* status,
-                             const BatchWork& w, hipStream_t s, KTimer* timer) {
+namespace {
+
+// The four kernels of one pass (kSkip == 0: cas ids, kSkip == 8: body digests).
+template <uint32_t kSkip>
+hipError_t batch_pass_launch(const uint8_t* arena, uint64_t arena_bytes, const uint64_t* off,
+                             const uint32_t* len, const uint8_t* whole, uint32_t n,
+                             uint32_t max_len, uint32_t out_words, uint8_t* out, uint8_t* has,
+                             int32_t* status, const BatchWork& w, hipStream_t s, KTimer* timer) {
   if (n == 0) return hipSuccess;
   uint32_t* o = reinterpret_cast<uint32_t*>(out);
   const uint32_t nb = std::min<uint32_t>(kSortBlocks, (n + kThreads - 1) / kThreads);
   const uint32_t nh = 2 * kBins * nb;
   const uint64_t cap = w.max_chunks;
   // hist_scan[kBins * nb] = R (start of the fold list), hist_scan[nh] = R + F
-  k_plan3<<<nb, kThreads, 0, s>>>(off, len, n, max_len, arena_bytes, w.n_chunks, w.hist, w.grab,
-                                  status, out_words, o);
+  k_plan3<kSkip><<<nb, kThreads, 0, s>>>(off, len, n, max_len, arena_bytes, w.n_chunks, w.hist,
+                                         w.grab, status, out_words, o, whole, has, w.total, cap);
   scan::exclusive(w.n_chunks, n, w.chunk_base, w.block_sums, w.total, s);
   scan::exclusive(w.hist, nh, w.hist, w.hist_sums, nullptr, s);
-  k_scatter3<<<nb, kThreads, 0, s>>>(off, len, n, max_len, arena_bytes, cap, w.total, status,
-                                     out_words, o, w.chunk_base, w.hist, w.order, w.chunk_msg);
+  k_scatter3<kSkip><<<nb, kThreads, 0, s>>>(off, len, n, max_len, arena_bytes, cap, w.total, status,
+                                            out_words, o, w.chunk_base, w.hist, w.order,
+                                            w.chunk_msg, whole, has, w.grab);
   const uint32_t* d_r = w.hist + static_cast<size_t>(kBins) * nb;
   {
-    KScope k(timer, "cas_leaves", s);
-    k_leaves3<<<leaves3_grid(), kThreads, 0, s>>>(arena, off, len, w.chunk_msg, w.chunk_base,
-                                                  w.total, w.order, d_r, w.grab, w.cvs, out_words,
-                                                  o, n, cap);
+    KScope k(timer, kSkip ? "body_leaves" : "cas_leaves", s);
+    k_leaves3<kSkip><<<leaves3_grid(), kThreads, 0, s>>>(arena, off, len, w.chunk_msg, w.chunk_base,
+                                                         w.total, w.order, d_r, w.grab, w.cvs,
+                                                         out_words, o, n, cap);
   }
   {
-    KScope k(timer, "cas_fold", s);
-    k_fold3<<<(n + kThreads - 1) / kThreads, kThreads, 0, s>>>(len, w.chunk_base, w.order, d_r,
-                                                               w.hist + nh, w.cvs, out_words, o,
-                                                               w.total, n, cap);
+    KScope k(timer, kSkip ? "body_fold" : "cas_fold", s);
+    k_fold3<kSkip><<<(n + kThreads - 1) / kThreads, kThreads, 0, s>>>(
+        len, w.chunk_base, w.order, d_r, w.hist + nh, w.cvs, out_words, o, w.total, n, cap, w.grab);
   }
   return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t batch_hash_launch(const uint8_t* arena, uint64_t arena_bytes, const uint64_t* off,
+                             const uint32_t* len, uint32_t n, uint32_t max_len,
+                             uint32_t out_words, uint8_t* out, int32_t* status,
+                             const BatchWork& w, hipStream_t s, KTimer* timer) {
+  return batch_pass_launch<0>(arena, arena_bytes, off, len, nullptr, n, max_len, out_words, out,
+                              nullptr, status, w, s, timer);
+}
+
+hipError_t batch_body_launch(const uint8_t* arena, uint64_t arena_bytes, const uint64_t* off,
+                             const uint32_t* len, const uint8_t* whole, uint32_t n,
+                             uint32_t max_len, uint8_t* out32, uint8_t* has, const BatchWork& w,
+                             hipStream_t s, KTimer* timer) {
+  return batch_pass_launch<8>(arena, arena_bytes, off, len, whole, n, max_len, 8, out32, has,
+                              nullptr, w, s, timer);
 }
 
 }  // namespace sdgpu

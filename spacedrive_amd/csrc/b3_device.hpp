@@ -105,8 +105,25 @@ __device__ __forceinline__ void b3_parent(uint32_t out[8], const uint32_t l[8],
   b3_compress(out, m, 0u, 0u, B3_BLOCK_LEN, B3_PARENT | extra_flags);
 }
 
-// 64 bytes at a 16-byte aligned address -> 16 little-endian words.
+// 64 bytes at a kAlign-byte aligned address -> 16 little-endian words.  kAlign
+// is 16 (dwordx4 loads: every cas message) or 8 (8-byte loads: the body of a
+// cas message, which starts 8 bytes into it); the loads cover [p, p + 64) and
+// nothing else, also where the compiler merges neighbours.
+template <uint32_t kAlign = 16>
 __device__ __forceinline__ void b3_load_block(const uint8_t* __restrict__ p, uint32_t m[16]) {
+  static_assert(kAlign == 16 || kAlign == 8, "16- or 8-byte loads");
+  if constexpr (kAlign == 8) {
+    const uint2* q = reinterpret_cast<const uint2*>(p);
+    uint2 x[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) x[k] = q[k];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      m[2 * k] = x[k].x;
+      m[2 * k + 1] = x[k].y;
+    }
+    return;
+  }
   const uint4* q = reinterpret_cast<const uint4*>(p);
   const uint4 a = q[0], b = q[1], c = q[2], d = q[3];
   m[0] = a.x; m[1] = a.y; m[2] = a.z; m[3] = a.w;
@@ -116,10 +133,17 @@ __device__ __forceinline__ void b3_load_block(const uint8_t* __restrict__ p, uin
 }
 
 // First `n` (0..64) bytes at a 4-byte aligned address, zero padded.  Never
-// touches a byte at or beyond p + n (no over-read past a message end).
+// touches a byte at or beyond p + n (no over-read past a message end).  With
+// kAlign == 8 the caller promises an 8-byte aligned p (a full block then takes
+// the 8-byte loader).
+template <uint32_t kAlign = 16>
 __device__ __forceinline__ void b3_load_block_partial(const uint8_t* __restrict__ p, uint32_t n,
                                                       uint32_t m[16]) {
   if (n == 64u) {
+    if constexpr (kAlign == 8) {
+      b3_load_block<8>(p, m);
+      return;
+    }
     if ((reinterpret_cast<uintptr_t>(p) & 15u) == 0) {
       b3_load_block(p, m);
       return;
@@ -139,7 +163,8 @@ __device__ __forceinline__ void b3_load_block_partial(const uint8_t* __restrict_
 }
 
 // Chaining value (or, with ROOT in `root_flag`, the digest words) of one chunk
-// of `clen` (0..1024) bytes at 16-byte aligned `p`, chunk counter `ctr`.
+// of `clen` (0..1024) bytes at kAlign-byte aligned `p`, chunk counter `ctr`.
+template <uint32_t kAlign = 16>
 __device__ __forceinline__ void b3_chunk(const uint8_t* __restrict__ p, uint32_t clen,
                                          uint64_t ctr, uint32_t root_flag, uint32_t cv[8]) {
   b3_iv(cv);
@@ -148,26 +173,44 @@ __device__ __forceinline__ void b3_chunk(const uint8_t* __restrict__ p, uint32_t
   uint32_t m[16];
   uint32_t b = 0;
   for (; b + 1 < nb; ++b) {
-    b3_load_block(p + 64u * b, m);
+    b3_load_block<kAlign>(p + 64u * b, m);
     b3_compress(cv, m, lo, hi, B3_BLOCK_LEN, b == 0 ? B3_CHUNK_START : 0u);
   }
   const uint32_t last = clen - 64u * b;
-  b3_load_block_partial(p + 64u * b, last, m);
+  b3_load_block_partial<kAlign>(p + 64u * b, last, m);
   b3_compress(cv, m, root_flag ? 0u : lo, root_flag ? 0u : hi, last,
               B3_CHUNK_END | (nb == 1 ? B3_CHUNK_START : 0u) | root_flag);
 }
 
-// A FULL 1024-byte chunk (16 blocks) at 16-byte aligned `p`, non-root.  Loads
+// A FULL 1024-byte chunk (16 blocks) at kAlign-byte aligned `p`, non-root.  Loads
 // one 128-byte line per lane (two blocks, 8 x dwordx4) per step: measured on
 // MI355X with lanes 4 KiB apart in HBM, 128-B steps sustain ~54.5 G
 // compressions/s against ~50.5 G for 64-B steps (scripts/exp_units.hip; the
-// register-only roof is ~56.4 G).
+// register-only roof is ~56.4 G).  kAlign == 8 (a message body): the same
+// 128-byte step as 16 8-byte loads, the same 32 registers -- p + 8 is never
+// 16-byte aligned, and dwordx4 loads from p - 8 with the words shifted by two
+// would read 8 bytes past a body that ends with this chunk.
+template <uint32_t kAlign = 16>
 __device__ __forceinline__ void b3_chunk_full(const uint8_t* __restrict__ p, uint64_t ctr,
                                               uint32_t cv[8]) {
   b3_iv(cv);
   const uint32_t lo = static_cast<uint32_t>(ctr), hi = static_cast<uint32_t>(ctr >> 32);
   for (uint32_t b = 0; b < 16; b += 2) {
     uint32_t m0[16], m1[16];
+    if constexpr (kAlign == 8) {
+      const uint2* q = reinterpret_cast<const uint2*>(p + 64u * b);
+      uint2 x[16];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) x[k] = q[k];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        m0[2 * k] = x[k].x; m0[2 * k + 1] = x[k].y;
+        m1[2 * k] = x[k + 8].x; m1[2 * k + 1] = x[k + 8].y;
+      }
+      b3_compress(cv, m0, lo, hi, B3_BLOCK_LEN, b == 0 ? B3_CHUNK_START : 0u);
+      b3_compress(cv, m1, lo, hi, B3_BLOCK_LEN, b == 14 ? B3_CHUNK_END : 0u);
+      continue;
+    }
     const uint4* q = reinterpret_cast<const uint4*>(p + 64u * b);
     uint4 x[8];
 #pragma unroll

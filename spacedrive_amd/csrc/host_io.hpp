@@ -320,9 +320,15 @@ inline void parallel_for(uint32_t n, F&& f) {
 struct SlabLayout {
   size_t arena_cap, off, len, out, status, total;
   uint32_t files_cap;
+  // with checksums only (0 otherwise): whole flags in, digests and
+  // has_checksum out, after the regions every slab has
+  size_t whole = 0, sum = 0, has = 0;
 };
 
-inline SlabLayout slab_layout(size_t arena_cap, uint32_t files_cap) {
+// checksums: the three regions of an identify call that also returns the
+// integrity_checksum of the files it read whole; the other offsets do not
+// depend on it.
+inline SlabLayout slab_layout(size_t arena_cap, uint32_t files_cap, bool checksums = false) {
   SlabLayout L;
   L.arena_cap = arena_cap;
   L.files_cap = files_cap;
@@ -331,6 +337,12 @@ inline SlabLayout slab_layout(size_t arena_cap, uint32_t files_cap) {
   L.out = align_up(L.len + 4ull * files_cap, 256);
   L.status = align_up(L.out + 8ull * files_cap, 256);
   L.total = align_up(L.status + 4ull * files_cap, 256);
+  if (checksums) {
+    L.whole = L.total;
+    L.sum = align_up(L.whole + 1ull * files_cap, 256);
+    L.has = align_up(L.sum + 32ull * files_cap, 256);
+    L.total = align_up(L.has + 1ull * files_cap, 256);
+  }
   return L;
 }
 

@@ -41,7 +41,8 @@ struct BatchWork {
   uint32_t* order = nullptr;       // [2n]  lane orders: message items, then fold lanes
   uint32_t* hist = nullptr;        // [2 * 128 * 256 + 1] per-block sort histograms
   uint32_t* hist_sums = nullptr;   // [scan tiles of hist]
-  uint32_t* grab = nullptr;        // [1] work-queue counter
+  uint32_t* grab = nullptr;        // [2] work-queue counter; the cas pass was over capacity
+                                   //     (left by the body pass's plan kernel for its others)
   uint64_t max_chunks = 0;         // capacity of chunk_msg / cvs (units + n must fit)
 };
 
@@ -58,6 +59,18 @@ hipError_t batch_hash_launch(const uint8_t* arena, uint64_t arena_bytes, const u
                              const uint32_t* len, uint32_t n, uint32_t max_len,
                              uint32_t out_words, uint8_t* out, int32_t* status,
                              const BatchWork& w, hipStream_t s, KTimer* timer = nullptr);
+
+// The body pass of K1 (integrity_checksum of the files read whole): for every
+// message with whole[i] != 0 that batch_hash_launch accepts and that holds the
+// 8-byte size prefix, out32[i] = BLAKE3(arena[off[i] + 8 .. off[i] + len[i]))
+// and has[i] = 1; every other message gets 32 zero bytes and has[i] = 0.  Runs
+// after batch_hash_launch over the same arguments on the same stream, in the
+// same workspace: when that pass was over capacity (-ENOBUFS) this one hashes
+// nothing and every has[i] is 0.  Reads no byte at or beyond off[i] + len[i].
+hipError_t batch_body_launch(const uint8_t* arena, uint64_t arena_bytes, const uint64_t* off,
+                             const uint32_t* len, const uint8_t* whole, uint32_t n,
+                             uint32_t max_len, uint8_t* out32, uint8_t* has, const BatchWork& w,
+                             hipStream_t s, KTimer* timer = nullptr);
 
 // Latency path for a few messages of at most 1 MiB each (SMALL_MAX_BYTES):
 // ONE launch.  max_chunks = largest chunk count in the batch.  Same status /

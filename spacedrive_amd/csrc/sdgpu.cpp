@@ -58,7 +58,7 @@ int batch_work(sdgpu_ctx* c, uint32_t n, uint64_t max_chunks, BatchWork& w) {
   const size_t o_hist = align_up(o_order + 8ull * n, 256);
   const size_t o_hsum = align_up(o_hist + 4ull * (n_hist + 1), 256);
   const size_t o_grab = align_up(o_hsum + 4ull * (scan::tiles_for(n_hist) + 1), 256);
-  const size_t o_map = align_up(o_grab + 4, 256);
+  const size_t o_map = align_up(o_grab + 8, 256);  // counter + the body pass's flag
   const size_t o_cvs = align_up(o_map + 4ull * max_chunks, 256);
   const size_t total = align_up(o_cvs + 32ull * max_chunks, 256);
   SD_TRY_RC(ensure_dev(c, c->batch_ws, total));
@@ -93,7 +93,8 @@ int tree_launch(sdgpu_ctx* c, const TreeSeg* segs, uint32_t nseg, bool cv_input,
   return 0;
 }
 
-int cas_grown_locked(sdgpu_ctx* c, const char* path, uint64_t size, uint8_t out8[8]);
+int cas_grown_locked(sdgpu_ctx* c, const char* path, uint64_t size, uint8_t out8[8],
+                     uint8_t* out32 = nullptr);
 
 // ---------------------------------------------------------------------------
 // K1 staging pipeline: slabs of messages packed into pinned memory by a
@@ -105,7 +106,7 @@ int cas_grown_locked(sdgpu_ctx* c, const char* path, uint64_t size, uint8_t out8
 // ---------------------------------------------------------------------------
 
 struct Slab {
-  uint8_t* h = nullptr;  // pinned [arena | off | len | out | status]
+  uint8_t* h = nullptr;  // pinned [arena | off | len | out | status (| whole | sum | has)]
   uint8_t* d = nullptr;  // same layout on the device
   hipEvent_t done = nullptr;
   bool busy = false;
@@ -127,11 +128,18 @@ int pipe_slot(sdgpu_ctx* c, int k, size_t bytes) {
 // file costs one ~60 KiB slab, not 256 MiB.
 // fill_batch (optional): fill_batch(first, cnt, off, cap_end, hb, len, pst) fills
 // a whole slab's messages at once (the io_uring reader) instead of produce().
-template <typename Est, typename Produce, typename Finish, typename FillBatch = std::nullptr_t>
+// whole (optional): whole(i) says that message i is size_le || a whole file; the
+// slab then also carries the flags in and the body digests and has_checksum
+// flags out (K1's body pass after the cas pass, every slab on the batch path
+// whatever its file count), and finish takes them as two more arguments.
+// Without it nothing of that is compiled in.
+template <typename Est, typename Produce, typename Finish, typename FillBatch = std::nullptr_t,
+          typename Whole = std::nullptr_t>
 int run_pipeline(sdgpu_ctx* c, uint32_t n, Est&& est, Produce&& produce, Finish&& finish,
-                 FillBatch&& fill_batch = nullptr) {
+                 FillBatch&& fill_batch = nullptr, Whole&& whole = nullptr) {
   (void)pick(c, nullptr);  // runs on the context stream, after earlier work on others
   constexpr int S = sdgpu_ctx::kPipeSlabs;
+  constexpr bool kSums = !std::is_same_v<std::decay_t<Whole>, std::nullptr_t>;
   uint64_t want = 0, biggest = 0;
   for (uint32_t i = 0; i < n; ++i) {
     const uint64_t e = align_up(est(i), 16);
@@ -153,7 +161,7 @@ int run_pipeline(sdgpu_ctx* c, uint32_t n, Est&& est, Produce&& produce, Finish&
   const uint64_t target = want <= (kSlabMinBytes << 1) ? want : std::max(want / div, kSlabMinBytes);
   const SlabLayout L = slab_layout(
       static_cast<size_t>(std::clamp<uint64_t>(std::max(target, biggest), 4096, kSlabBytes)),
-      std::clamp<uint32_t>(n, 1, kSlabFiles));
+      std::clamp<uint32_t>(n, 1, kSlabFiles), kSums);
   Slab slabs[S];
   int rc = 0;
   for (int k = 0; k < S && rc == 0; ++k) {
@@ -175,8 +183,13 @@ int run_pipeline(sdgpu_ctx* c, uint32_t n, Est&& est, Produce&& produce, Finish&
     if (hipEventSynchronize(sl.done) != hipSuccess) return -EIO;
     if (ht) ht->host("stage_wait", ms_since(t0));
     sl.busy = false;
-    finish(sl.first, sl.count, reinterpret_cast<const uint8_t(*)[8]>(sl.h + L.out),
-           reinterpret_cast<const int32_t*>(sl.h + L.status));
+    if constexpr (kSums)
+      finish(sl.first, sl.count, reinterpret_cast<const uint8_t(*)[8]>(sl.h + L.out),
+             reinterpret_cast<const int32_t*>(sl.h + L.status),
+             reinterpret_cast<const uint8_t(*)[32]>(sl.h + L.sum), sl.h + L.has);
+    else
+      finish(sl.first, sl.count, reinterpret_cast<const uint8_t(*)[8]>(sl.h + L.out),
+             reinterpret_cast<const int32_t*>(sl.h + L.status));
     return 0;
   };
   // Taper (off by default): the device work left after the last read is the
@@ -238,7 +251,9 @@ int run_pipeline(sdgpu_ctx* c, uint32_t n, Est&& est, Produce&& produce, Finish&
     uint8_t* db = sl.d;
     uint32_t max_msg = 0;
     for (uint32_t j = 0; j < cnt; ++j) max_msg = std::max(max_msg, len[j]);
-    const bool small = cnt <= kSmallBatch && max_msg <= SMALL_MAX_BYTES;
+    if constexpr (kSums)
+      for (uint32_t j = 0; j < cnt; ++j) hb[L.whole + j] = whole(sl.first + j) ? 1 : 0;
+    const bool small = !kSums && cnt <= kSmallBatch && max_msg <= SMALL_MAX_BYTES;
     const size_t prefix = L.len + 4ull * cnt;
     // a few cas messages (the single-file and small-batch callers): read from
     // the pinned slab and the ids written back into it by the kernel itself,
@@ -264,6 +279,15 @@ int run_pipeline(sdgpu_ctx* c, uint32_t n, Est&& est, Produce&& produce, Finish&
                                        2, db + L.out, nullptr, small_scratch(c, s), s, c->kt())
                   : batch_hash_launch(db, L.arena_cap, d_off, d_len, cnt, kStageMaxMsg, 2,
                                       db + L.out, nullptr, w, s, c->kt())) == hipSuccess;
+    if constexpr (kSums)  // the body pass, then its two regions back
+      ok = ok &&
+           hipMemcpyAsync(db + L.whole, hb + L.whole, cnt, hipMemcpyHostToDevice, s) ==
+               hipSuccess &&
+           batch_body_launch(db, L.arena_cap, d_off, d_len, db + L.whole, cnt, kStageMaxMsg,
+                             db + L.sum, db + L.has, w, s, c->kt()) == hipSuccess &&
+           hipMemcpyAsync(hb + L.sum, db + L.sum, 32ull * cnt, hipMemcpyDeviceToHost, s) ==
+               hipSuccess &&
+           hipMemcpyAsync(hb + L.has, db + L.has, cnt, hipMemcpyDeviceToHost, s) == hipSuccess;
     if (!ok ||
         (!host1 &&
          hipMemcpyAsync(hb + L.out, db + L.out, 8ull * cnt, hipMemcpyDeviceToHost, s) != hipSuccess) ||
@@ -439,6 +463,31 @@ int sdgpu_cas_batch_device(sdgpu_ctx* c, const uint8_t* d_arena, uint64_t arena_
   return 0;
 }
 
+int sdgpu_cas_checksum_batch_device(sdgpu_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes,
+                                    const uint64_t* d_off, const uint32_t* d_len,
+                                    const uint8_t* d_whole, uint32_t n, uint8_t* d_out8,
+                                    uint8_t* d_out32, uint8_t* d_has_checksum, int32_t* d_status,
+                                    void* stream) {
+  if (!c || (n && (!d_arena || !d_off || !d_len || !d_out8 || !d_whole || !d_out32 ||
+                   !d_has_checksum)))
+    return -EINVAL;
+  if (reinterpret_cast<uintptr_t>(d_arena) % 16 || reinterpret_cast<uintptr_t>(d_out8) % 4 ||
+      reinterpret_cast<uintptr_t>(d_out32) % 4)
+    return -EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  SD_TRY(hipSetDevice(c->device));
+  hipStream_t s = pick(c, stream);
+  BatchWork w;
+  SD_TRY_RC(batch_work(c, n, arena_bytes / kChunkLen + n, w));
+  // the cas pass exactly as sdgpu_cas_batch_device, then the body pass in the
+  // same workspace on the same stream
+  SD_TRY(batch_hash_launch(d_arena, arena_bytes, d_off, d_len, n, CAS_MAX_MSG_LEN, 2, d_out8,
+                           d_status, w, s, c->kt()));
+  SD_TRY(batch_body_launch(d_arena, arena_bytes, d_off, d_len, d_whole, n, CAS_MAX_MSG_LEN,
+                           d_out32, d_has_checksum, w, s, c->kt()));
+  return 0;
+}
+
 // Pinned-host staged K1 (config 5): slabs of the caller's pinned arena are
 // copied H2D on the context's copy stream (SDMA) into a ring of three device
 // slabs while K1 hashes the previous slab on the compute stream; events order
@@ -566,11 +615,17 @@ int sdgpu_cas_batch(sdgpu_ctx* c, const uint8_t* msg_arena, const uint64_t* msg_
   return rc;
 }
 
-int sdgpu_identify_files(sdgpu_ctx* c, const char* const* paths, const uint64_t* size_in,
-                         uint32_t n, uint8_t (*out8)[8], uint8_t* has_key, int32_t* status) {
-  if (!c || (n && (!paths || !out8))) return -EINVAL;
-  std::lock_guard<std::mutex> g(c->mu);
-  SD_TRY(hipSetDevice(c->device));
+extern "C++" {
+namespace {
+
+// sdgpu_identify_files (kSums false: out32 / has_checksum unused) and
+// sdgpu_identify_checksum_files (kSums true) -- one body, so the reads, the
+// statuses and the cas ids of the two cannot drift apart; the checksum parts
+// are compiled into the second only.
+template <bool kSums>
+int identify_files_locked(sdgpu_ctx* c, const char* const* paths, const uint64_t* size_in,
+                          uint32_t n, uint8_t (*out8)[8], uint8_t* has_key, int32_t* status,
+                          uint8_t (*out32)[32], uint8_t* has_checksum) {
   // size NULL (ABI 6): the fresh fs::metadata(path).len() of the reference
   // (file_identifier/mod.rs:65,80-81), stat-ed here by the read pool; a path
   // whose stat fails gets status -errno and no key (the row is dropped,
@@ -592,31 +647,44 @@ int sdgpu_identify_files(sdgpu_ctx* c, const char* const* paths, const uint64_t*
   const uint64_t* size = size_in ? size_in : fresh.data();
   auto failed = [&](uint32_t i) -> int32_t { return stat_rc.empty() ? 0 : stat_rc[i]; };
   std::vector<uint32_t> grown;  // <= 100 KiB at stat, longer than its room at read
-  const int rc = run_pipeline(
-      c, n,
-      [&](uint32_t i) -> uint64_t {
-        if (size[i] == 0 || failed(i)) return 16;
-        return size[i] <= SDGPU_CAS_MINIMUM_FILE_SIZE ? 8 + size[i] + 4096  // room to grow
-                                                      : SDGPU_CAS_SAMPLED_MSG_LEN;
-      },
-      [&](uint32_t i, uint8_t* dst, size_t cap) -> int64_t {
-        if (failed(i)) return failed(i);
-        if (size[i] == 0) return 0x7fffffff;  // cas_id None (file_identifier/mod.rs:80-88)
-        if (c->io_bounce) return read_cas_message_bounce(paths[i], size[i], dst, cap);
-        return read_cas_message(paths[i], size[i], dst, cap);
-      },
-      [&](uint32_t first, uint32_t cnt, const uint8_t (*o)[8], const int32_t* st) {
-        for (uint32_t j = 0; j < cnt; ++j) {
-          const int32_t sj = st[j];
-          const bool ok = sj == 0;
-          if (sj == -EFBIG) grown.push_back(first + j);
-          if (ok) memcpy(out8[first + j], o[j], 8);
-          else memset(out8[first + j], 0, 8);
-          if (has_key) has_key[first + j] = ok ? 1 : 0;
-          if (status) status[first + j] = sj == 1 ? 0 : sj;
-        }
-      },
-      [&](uint32_t first, uint32_t cnt, const uint64_t* off, uint64_t end, uint8_t* hb,
+  auto est = [&](uint32_t i) -> uint64_t {
+    if (size[i] == 0 || failed(i)) return 16;
+    return size[i] <= SDGPU_CAS_MINIMUM_FILE_SIZE ? 8 + size[i] + 4096  // room to grow
+                                                  : SDGPU_CAS_SAMPLED_MSG_LEN;
+  };
+  auto produce = [&](uint32_t i, uint8_t* dst, size_t cap) -> int64_t {
+    if (failed(i)) return failed(i);
+    if (size[i] == 0) return 0x7fffffff;  // cas_id None (file_identifier/mod.rs:80-88)
+    if (c->io_bounce) return read_cas_message_bounce(paths[i], size[i], dst, cap);
+    return read_cas_message(paths[i], size[i], dst, cap);
+  };
+  auto finish = [&](uint32_t first, uint32_t cnt, const uint8_t (*o)[8], const int32_t* st) {
+    for (uint32_t j = 0; j < cnt; ++j) {
+      const int32_t sj = st[j];
+      const bool ok = sj == 0;
+      if (sj == -EFBIG) grown.push_back(first + j);
+      if (ok) memcpy(out8[first + j], o[j], 8);
+      else memset(out8[first + j], 0, 8);
+      if (has_key) has_key[first + j] = ok ? 1 : 0;
+      if (status) status[first + j] = sj == 1 ? 0 : sj;
+    }
+  };
+  // the digest of a file read whole: the bytes of its cas message after the
+  // size prefix, so exactly what went into the cas_id
+  auto finish_sums = [&](uint32_t first, uint32_t cnt, const uint8_t (*o)[8], const int32_t* st,
+                         const uint8_t (*dg)[32], const uint8_t* has) {
+    finish(first, cnt, o, st);
+    for (uint32_t j = 0; j < cnt; ++j) {
+      const bool ok = st[j] == 0 && has[j] != 0;
+      if (ok) memcpy(out32[first + j], dg[j], 32);
+      else memset(out32[first + j], 0, 32);
+      has_checksum[first + j] = ok ? 1 : 0;
+    }
+  };
+  auto whole = [&](uint32_t i) -> bool {
+    return size[i] != 0 && size[i] <= SDGPU_CAS_MINIMUM_FILE_SIZE;
+  };
+  auto fill_uring = [&](uint32_t first, uint32_t cnt, const uint64_t* off, uint64_t end, uint8_t* hb,
           auto&& settle) -> bool {
         // batched io_uring chains (csrc/uring.hpp), one ring per pool thread:
         // the same bytes and statuses as read_cas_message
@@ -653,15 +721,47 @@ int sdgpu_identify_files(sdgpu_ctx* c, const char* const* paths, const uint64_t*
           for (uint32_t k = 0; k < m; ++k) settle(idx[k], jobs[k].result);
         });
         return true;
-      });
+      };
+  (void)finish_sums;
+  (void)whole;
+  int rc;
+  if constexpr (kSums) rc = run_pipeline(c, n, est, produce, finish_sums, fill_uring, whole);
+  else rc = run_pipeline(c, n, est, produce, finish, fill_uring);
   if (rc) return rc;
   for (const uint32_t i : grown) {
-    const int r = cas_grown_locked(c, paths[i], size[i], out8[i]);
+    // the buffer cas_grown_locked reads is hashed a second time without its
+    // prefix: no second read of the file
+    const int r = cas_grown_locked(c, paths[i], size[i], out8[i], kSums ? out32[i] : nullptr);
     if (r) memset(out8[i], 0, 8);
     if (has_key) has_key[i] = r == 0 ? 1 : 0;
     if (status) status[i] = r;
+    if constexpr (kSums) {
+      if (r) memset(out32[i], 0, 32);
+      has_checksum[i] = r == 0 ? 1 : 0;
+    }
   }
   return 0;
+}
+
+}  // namespace
+}  // extern "C++"
+
+int sdgpu_identify_files(sdgpu_ctx* c, const char* const* paths, const uint64_t* size_in,
+                         uint32_t n, uint8_t (*out8)[8], uint8_t* has_key, int32_t* status) {
+  if (!c || (n && (!paths || !out8))) return -EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  SD_TRY(hipSetDevice(c->device));
+  return identify_files_locked<false>(c, paths, size_in, n, out8, has_key, status, nullptr, nullptr);
+}
+
+int sdgpu_identify_checksum_files(sdgpu_ctx* c, const char* const* paths, const uint64_t* size_in,
+                                  uint32_t n, uint8_t (*out8)[8], uint8_t* has_key,
+                                  uint8_t (*out32)[32], uint8_t* has_checksum, int32_t* status) {
+  if (!c || (n && (!paths || !out8 || !out32 || !has_checksum))) return -EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  SD_TRY(hipSetDevice(c->device));
+  return identify_files_locked<true>(c, paths, size_in, n, out8, has_key, status, out32,
+                                     has_checksum);
 }
 
 // ---- the resident latency service (f3) ----------------------------------------
@@ -879,7 +979,10 @@ int checksum_host_locked(sdgpu_ctx* c, const void* bytes, uint64_t len, uint8_t 
 // reservation at read time: fs::read takes whatever the file holds then
 // (cas.rs:27-29), so the message is u64 size LE || the whole current content,
 // of any length; hashed by the tree kernels.  out8 = BLAKE3(M)[0..8).
-int cas_grown_locked(sdgpu_ctx* c, const char* path, uint64_t size, uint8_t out8[8]) {
+// out32 (optional): also BLAKE3 of that content alone, the file's
+// integrity_checksum at the moment of the read, from the same buffer.
+int cas_grown_locked(sdgpu_ctx* c, const char* path, uint64_t size, uint8_t out8[8],
+                     uint8_t* out32) {
   const int fd = open(path, O_RDONLY | O_CLOEXEC);
   if (fd < 0) return -errno;
   std::vector<uint8_t> msg(8);
@@ -901,6 +1004,7 @@ int cas_grown_locked(sdgpu_ctx* c, const char* path, uint64_t size, uint8_t out8
   if (rc) return rc;
   uint8_t d[32];
   SD_TRY_RC(checksum_host_locked(c, msg.data(), msg.size(), d));
+  if (out32) SD_TRY_RC(checksum_host_locked(c, msg.data() + 8, msg.size() - 8, out32));
   memcpy(out8, d, 8);
   return 0;
 }

@@ -7,6 +7,10 @@
 * ``identify(paths)``: the batched form of identifier_job_step's metadata
   phase (mod.rs:107-134) -- every file's cas windows are pread into pinned
   slabs and hashed by K1 while the next slab is read (sdgpu_identify_files).
+  With ``checksums=True`` the same read also gives the integrity_checksum of
+  every file read whole (sdgpu_identify_checksum_files), so the object
+  validator (validator_job.rs:100-169) is left with the sampled and the
+  empty files.
 * ``identifier_job(paths)``: the whole job over orphan rows in id order --
   cas ids, then the Object grouping of every row (dedup.group_reps), with the
   reference's per-step (created, linked) accounting.
@@ -55,10 +59,19 @@ class IdentifyResult:
     has_key: np.ndarray   # [n] uint8: 1 = cas_id present
     status: np.ndarray    # [n] int32: 0 or -errno (row dropped, mod.rs:113,127)
     sizes: np.ndarray | None  # [n] uint64 as passed; None: stat-ed by the library
+    checksum32: np.ndarray | None = None    # [n, 32] uint8 (identify(checksums=True))
+    has_checksum: np.ndarray | None = None  # [n] uint8: 1 = the file was read whole
 
     def cas_ids(self) -> list[str | None]:
         return [bytes(self.cas8[i]).hex() if self.has_key[i] else None
                 for i in range(self.has_key.size)]
+
+    def checksums(self) -> list[str | None]:
+        """integrity_checksum (64 hex chars) of the rows read whole, else None."""
+        if self.has_checksum is None:
+            return [None] * self.has_key.size
+        return [bytes(self.checksum32[i]).hex() if self.has_checksum[i] else None
+                for i in range(self.has_checksum.size)]
 
 
 class PathList:
@@ -81,9 +94,11 @@ class PathList:
         return self.paths[i]
 
 
-def identify(paths, sizes=None, ctx=None) -> IdentifyResult:
+def identify(paths, sizes=None, ctx=None, checksums: bool = False) -> IdentifyResult:
     """cas ids of many files in one pipelined call (paths: a sequence of
-    paths, or a PathList)."""
+    paths, or a PathList).  checksums: also the integrity_checksum of every
+    file read whole (0 < size <= 100 KiB), hashed from the bytes already on
+    the device (K1's body pass) -- no second read."""
     ctx = ctx or default_context()
     n = len(paths)
     # sizes None: the library stats every path in its read pool (the
@@ -95,8 +110,17 @@ def identify(paths, sizes=None, ctx=None) -> IdentifyResult:
     out = np.zeros((n, 8), np.uint8)
     has = np.zeros(n, np.uint8)
     status = np.zeros(n, np.int32)
-    check(ctx.lib.sdgpu_identify_files(ctx.h, arr, sizes.ctypes.data if sizes is not None else None,
-                                       n, out.ctypes.data, has.ctypes.data, status.ctypes.data),
+    psz = sizes.ctypes.data if sizes is not None else None
+    if checksums:
+        out32 = np.zeros((n, 32), np.uint8)
+        has32 = np.zeros(n, np.uint8)
+        check(ctx.lib.sdgpu_identify_checksum_files(ctx.h, arr, psz, n, out.ctypes.data,
+                                                    has.ctypes.data, out32.ctypes.data,
+                                                    has32.ctypes.data, status.ctypes.data),
+              "sdgpu_identify_checksum_files")
+        return IdentifyResult(out, has, status, sizes, out32, has32)
+    check(ctx.lib.sdgpu_identify_files(ctx.h, arr, psz, n, out.ctypes.data, has.ctypes.data,
+                                       status.ctypes.data),
           "sdgpu_identify_files")
     return IdentifyResult(out, has, status, sizes)
 
@@ -127,7 +151,8 @@ def identifier_job(paths, chunk_size: int = CHUNK_SIZE, ctx=None) -> JobResult:
 class FilePaths:
     """The file_path rows the identifier reads and writes: the columns of
     file_path_for_file_identifier (core/src/location/file_path_helper/mod.rs:32-40)
-    plus cas_id and object_id (core/prisma/schema.prisma:154-201).  An in-memory
+    plus cas_id, object_id and integrity_checksum
+    (core/prisma/schema.prisma:154-201).  An in-memory
     stand-in for the library's table -- the prisma/SQLite store is out of scope
     (SURVEY §2); the job only needs these queries and writes."""
 
@@ -138,6 +163,7 @@ class FilePaths:
         self.is_dir: list[bool] = []
         self.cas_id: list[str | None] = []
         self.object_id: list[int | None] = []
+        self.integrity_checksum: list[str | None] = []
         self.next_object_id = 1
         # per location, the ids of its non-directory rows (ascending: ids are
         # appended in order) -- the index the orphan query walks from the cursor
@@ -152,6 +178,7 @@ class FilePaths:
         self.is_dir.append(is_dir)
         self.cas_id.append(None)
         self.object_id.append(None)
+        self.integrity_checksum.append(None)
         fid = len(self.name)
         if not is_dir:
             self._file_rows.setdefault(location_id, []).append(fid)
@@ -191,6 +218,15 @@ class FilePaths:
             if limit is not None and len(out) >= limit:
                 break
         return out
+
+    def unvalidated(self, location_id: int, sub_path: str | None = None) -> list[int]:
+        """ids of the rows the object validator checksums, in ascending id
+        (validator_job.rs:100-116): the location, not a directory,
+        integrity_checksum NULL, and under sub_path if one is given."""
+        under = "/" + sub_path.strip("/") + "/" if sub_path and sub_path.strip("/") else None
+        return [fid for fid in self._file_rows.get(location_id, [])
+                if self.integrity_checksum[fid - 1] is None
+                and (under is None or self.materialized_path[fid - 1].startswith(under))]
 
     def count_orphans(self, location_id: int, children_of: str | None = None,
                       under: str | None = None) -> int:
@@ -287,12 +323,18 @@ class FileIdentifierJob:
     Objects are deleted).  Row ranks mean nothing to the next job, so after
     every step the Objects the step created are registered under their Object
     ids (add_objects: a registered Object supersedes the rank entry; steps are
-    whole chunks, so later rows link to the same Objects either way)."""
+    whole chunks, so later rows link to the same Objects either way).
+
+    checksums: every step also writes the integrity_checksum of the rows whose
+    file it read whole (identify(checksums=True)); the validator that follows
+    (its paths: FilePaths.unvalidated) then only has the sampled and the empty
+    files left."""
 
     def __init__(self, table: FilePaths, location_id: int, location_path: str,
                  sub_path: str | None = None, chunks_per_step: int = 64, ctx=None,
-                 _shallow_dir: str | None = None, index=None):
+                 _shallow_dir: str | None = None, index=None, checksums: bool = False):
         self.table = table
+        self.checksums = bool(checksums)
         self.location_id = location_id
         self.location_path = location_path
         self.sub_path = sub_path
@@ -357,7 +399,7 @@ class FileIdentifierJob:
         if not cand:
             raise EarlyFinish("Expected orphan Paths not returned from database query for this chunk")
         paths = [os.path.join(self.location_path, self.table.rel_path(f)) for f in cand]
-        ident = identify(paths, ctx=self.ctx)
+        ident = identify(paths, ctx=self.ctx, checksums=self.checksums)
         ok = {f: ident.status[i] == 0 for i, f in enumerate(cand)}
         pos = {f: i for i, f in enumerate(cand)}
         # replay the reference's fetches: chunk c = the next 100 orphans with
@@ -395,6 +437,8 @@ class FileIdentifierJob:
                 continue
             i = f - 1
             t.cas_id[i] = bytes(ident.cas8[pos[f]]).hex() if has[j] else None
+            if self.checksums and ident.has_checksum[pos[f]]:
+                t.integrity_checksum[i] = bytes(ident.checksum32[pos[f]]).hex()
             r = first_rank + j
             if rep[j] == r:
                 obj = t.next_object_id
@@ -437,12 +481,14 @@ class FileIdentifierJob:
         return {"location_id": self.location_id, "location_path": self.location_path,
                 "sub_path": self.sub_path, "shallow_dir": self._children_of,
                 "chunks_per_step": self.chunks_per_step, "step_number": self.step_number,
-                "task_count": self.task_count, "run_metadata": asdict(self.meta)}
+                "task_count": self.task_count, "run_metadata": asdict(self.meta),
+                "checksums": self.checksums}
 
     @classmethod
     def resume(cls, table: FilePaths, state: dict, ctx=None, index=None) -> "FileIdentifierJob":
         job = cls(table, state["location_id"], state["location_path"], state["sub_path"],
-                  state["chunks_per_step"], ctx, state.get("shallow_dir"), index=index)
+                  state["chunks_per_step"], ctx, state.get("shallow_dir"), index=index,
+                  checksums=state.get("checksums", False))
         job.meta = IdentifierRunMetadata(**state["run_metadata"])
         job.step_number = state["step_number"]
         job.task_count = state["task_count"]
@@ -460,14 +506,14 @@ class EarlyFinish(Exception):
 
 
 def shallow(table: FilePaths, location_id: int, location_path: str, sub_path: str = "",
-            chunks_per_step: int = 64, ctx=None) -> IdentifierRunMetadata:
+            chunks_per_step: int = 64, ctx=None, checksums: bool = False) -> IdentifierRunMetadata:
     """file_identifier::shallow (shallow.rs:26-119): the light scan of one
     directory -- only its direct children (materialized_path equal to the
     directory's children path, :121-139), all steps at once, outside the job
     system; no orphans is not an error (:65-67)."""
     d = "/" + sub_path.strip("/") + "/" if sub_path.strip("/") else "/"
     job = FileIdentifierJob(table, location_id, location_path, None, chunks_per_step, ctx,
-                            _shallow_dir=d)
+                            _shallow_dir=d, checksums=checksums)
     try:
         job.init()
     except EarlyFinish:
