@@ -302,6 +302,54 @@ pub fn identify_with_checksums(gpu: &Gpu, paths: &[PathBuf], sizes: Option<&[u64
     Ok(out)
 }
 
+/// `identify` plus every file's Object kind -- the three outputs of
+/// FileMetadata::new (mod.rs:59-97) from one call
+/// (`sdgpu_identify_kind_files`): `kind[i]` is the ObjectKind value
+/// (crates/file-ext/src/kind.rs) that `Extension::resolve_conflicting(&path,
+/// verify_magic)` (magic.rs:176-236) gives on the bytes the call read for the
+/// cas_id, for every row with status 0 (empty files included), 0 for failed
+/// rows.  `checksums` as in `identify_with_checksums` (None without).
+pub struct IdentifiedWithKinds {
+    pub rows: Identified,
+    pub kind: Vec<i32>,
+    pub checksums: Option<(Vec<[u8; 32]>, Vec<u8>)>,
+}
+
+pub fn identify_with_kinds(gpu: &Gpu, paths: &[PathBuf], sizes: Option<&[u64]>, verify_magic: bool)
+                           -> io::Result<IdentifiedWithKinds> {
+    identify_kinds(gpu, paths, sizes, verify_magic, false)
+}
+
+/// `with_checksums`: also the integrity_checksum of the files read whole.
+pub fn identify_kinds(gpu: &Gpu, paths: &[PathBuf], sizes: Option<&[u64]>, verify_magic: bool,
+                      with_checksums: bool) -> io::Result<IdentifiedWithKinds> {
+    let n = paths.len();
+    if sizes.map_or(false, |s| s.len() != n) {
+        return Err(io::Error::new(io::ErrorKind::InvalidInput, "one size per path"));
+    }
+    let c: Vec<_> = paths.iter().map(|p| cpath(p)).collect();
+    let ptrs: Vec<*const c_char> = c.iter().map(|s| s.as_ptr()).collect();
+    let mut out = IdentifiedWithKinds {
+        rows: Identified { cas8: vec![[0u8; 8]; n], has_key: vec![0u8; n], status: vec![0i32; n] },
+        kind: vec![0i32; n],
+        checksums: with_checksums.then(|| (vec![[0u8; 32]; n], vec![0u8; n])),
+    };
+    let (p32, phas) = match out.checksums.as_mut() {
+        Some((d, h)) => (d.as_mut_ptr(), h.as_mut_ptr()),
+        None => (ptr::null_mut(), ptr::null_mut()),
+    };
+    let flags = if verify_magic { sys::SDGPU_KIND_VERIFY_MAGIC } else { 0 };
+    let ctx = gpu.ctx();
+    check(unsafe {
+        sys::sdgpu_identify_kind_files(*ctx, ptrs.as_ptr(),
+                                       sizes.map_or(std::ptr::null(), |s| s.as_ptr()), n as u32, flags,
+                                       out.rows.cas8.as_mut_ptr(), out.rows.has_key.as_mut_ptr(),
+                                       p32, phas, out.kind.as_mut_ptr(),
+                                       out.rows.status.as_mut_ptr())
+    })?;
+    Ok(out)
+}
+
 /// The grouping of one batch of identified rows against the index (rows in
 /// id order, ranks first_rank + i); rows whose read failed take no part.
 pub fn group(gpu: &Gpu, idx: &ObjectIndex<'_>, rows: &Identified, first_rank: u32) -> io::Result<Vec<IdentifiedRow>> {

@@ -21,7 +21,7 @@ use std::{collections::HashMap, io, path::PathBuf};
 use serde::{Deserialize, Serialize};
 
 use crate::{
-    identifier::{group, identify, Identified, IdentifiedRow, Link, ObjectIndex},
+    identifier::{group, identify, identify_with_kinds, Identified, IdentifiedRow, Link, ObjectIndex},
     Gpu,
 };
 
@@ -64,8 +64,11 @@ pub trait OrphanTable {
     /// `file_path.cas_id` of the step's rows, all in ONE write
     /// (mod.rs:144-165: one `write_ops` batch of updates per step).
     fn set_cas_ids(&mut self, rows: &[(i32, Option<String>)]) -> io::Result<()>;
-    /// `object::create_many` of `n` Objects (mod.rs:243-297); returns their ids.
-    fn create_objects(&mut self, n: usize) -> io::Result<Vec<u32>>;
+    /// `object::create_many` of one Object per entry (mod.rs:243-297); returns
+    /// their ids.  An entry is the new Object's `kind` (mod.rs:265-275,
+    /// `object::kind::set(Some(kind))`: the ObjectKind of the row that creates
+    /// it), None when the job runs without kinds (the column stays unset).
+    fn create_objects(&mut self, kinds: &[Option<i32>]) -> io::Result<Vec<u32>>;
     /// `file_path.object_id` connects (mod.rs:189-225, 297-333).
     fn connect(&mut self, links: &[(i32, u32)]) -> io::Result<()>;
 }
@@ -86,6 +89,9 @@ pub struct JobState {
     pub step_number: usize,
     pub task_count: usize,
     pub chunks_per_step: usize,
+    /// identify through `identify_with_kinds` and store each new Object's kind
+    #[serde(default)]
+    pub kinds: bool,
 }
 
 pub struct FileIdentifierJob<'a, T: OrphanTable> {
@@ -177,7 +183,14 @@ impl<'a, T: OrphanTable> FileIdentifierJob<'a, T> {
         // independent); sizes None: the library stats every path in its read
         // pool, the reference's fresh fs::metadata (mod.rs:65,80-81)
         let paths: Vec<PathBuf> = cand.iter().map(|o| o.path.clone()).collect();
-        let ident = identify(self.gpu, &paths, None)?;
+        let (ident, kind) = if self.state.kinds {
+            // FileMetadata::new whole (mod.rs:59-97): the kind comes out of the
+            // same read as the cas_id, no second open per file
+            let k = identify_with_kinds(self.gpu, &paths, None, false)?;
+            (k.rows, Some(k.kind))
+        } else {
+            (identify(self.gpu, &paths, None)?, None)
+        };
         let ok: Vec<bool> = ident.status.iter().map(|&s| s == 0).collect();
         // replay the reference's fetches
         let mut fetched: Vec<Vec<usize>> = Vec::new();
@@ -231,7 +244,11 @@ impl<'a, T: OrphanTable> FileIdentifierJob<'a, T> {
         }
         self.table.set_cas_ids(&cas_ids)?;
         let linked = links.len() + to_rows.len();
-        let ids = self.table.create_objects(creators.len())?;
+        // each new Object carries its creator row's kind (mod.rs:265-275)
+        let by_rank = |rank: u32| rows[(rank - first_rank) as usize];
+        let new_kinds: Vec<Option<i32>> =
+            creators.iter().map(|&(rank, _)| kind.as_ref().map(|k| k[by_rank(rank)])).collect();
+        let ids = self.table.create_objects(&new_kinds)?;
         for (&(rank, id), &obj) in creators.iter().zip(&ids) {
             self.creator_object.insert(rank, obj);
             links.push((id, obj));

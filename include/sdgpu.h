@@ -158,6 +158,59 @@ int sdgpu_identify_checksum_files(sdgpu_ctx *ctx, const char *const *paths, cons
                                   uint32_t n, uint8_t (*out8)[8], uint8_t *has_key,
                                   uint8_t (*out32)[32], uint8_t *has_checksum, int32_t *status);
 
+/* ---- Object kind (ABI 6, additive) -------------------------------------------
+ * The third output of FileMetadata::new (file_identifier/mod.rs:75-78):
+ * Extension::resolve_conflicting(&path, false) of sd-file-ext, as ObjectKind
+ * values (crates/file-ext/src/kind.rs).  One table (215 extension variants,
+ * 127 signature alternatives) and one matcher serve the host calls and the
+ * kernel.  flags: 0 = the identifier's mode (always_check_magic_bytes =
+ * false: a name of one category gives that category with no byte looked at;
+ * `ts` / `mts` are Video when the Video signature matches, else Code), or
+ * SDGPU_KIND_VERIFY_MAGIC = the function's second parameter set (names of
+ * Image, Audio, Video, Archive, Executable, Font, Encrypted, Mesh, Database
+ * keep their category only when their signature matches, else kind 0).  Any
+ * other flag bit is -EINVAL.  A path without an Extension has kind 0 (Unknown). */
+#define SDGPU_KIND_VERIFY_MAGIC 1u
+/* (ABI 6, additive) ext_id_out[i] = extension id of paths[i] (magic.rs:180-186:
+ * Path::extension, to_str, to_lowercase, Extension::from_str): 0 = no
+ * Extension, else 1..215, stable.  Host only, no context. */
+int sdgpu_kind_ext_ids(const char *const *paths, uint32_t n, uint16_t *ext_id_out);
+/* (ABI 6, additive) Enumerates the table (extensions.rs:11-362): out = the
+ * lower-case name of ext_id (NUL-padded), kinds[0] its ObjectKind, kinds[1] 0
+ * except for the entries `ts` / `mts` resolve to, where it is Code (kinds[0]
+ * Video); -ENOENT for 0 and past the end.  A path resolves to the first entry
+ * of its name. */
+int sdgpu_kind_ext_name(uint32_t ext_id, char out[16], int32_t kinds[2]);
+/* (ABI 6, additive) resolve_conflicting(path, flags) as the reference does it
+ * (magic.rs:176-236): the file is opened when its name has an Extension, and
+ * read (its first bytes only) when the decision needs them.  *kind = 0 and
+ * return 0 when the open fails (magic.rs:188-190).  Host only. */
+int sdgpu_kind_of_file(const char *path, uint32_t flags, int32_t *kind);
+/* (ABI 6, additive) Kinds of n device-resident cas messages (magic.rs:160-236):
+ * d_ext is device u16[n] (sdgpu_kind_ext_ids), d_kind device u8[n].  The file
+ * bytes of message i are arena[off + 8 .. off + len); a message shorter than
+ * 8 bytes has none.  Validity as in sdgpu_cas_batch_device (offset 16-B
+ * aligned, len <= SDGPU_CAS_MAX_MSG_LEN, inside arena_bytes): an invalid
+ * message gets kind 0.  Reads at most the first 48 bytes of a message, never
+ * a byte at or beyond off + len; the arena is not written.  Asynchronous on
+ * `stream`. */
+int sdgpu_kind_batch_device(sdgpu_ctx *ctx, const uint8_t *d_arena, uint64_t arena_bytes,
+                            const uint64_t *d_off, const uint32_t *d_len, const uint16_t *d_ext,
+                            uint32_t n, uint32_t flags, uint8_t *d_kind, void *stream);
+/* (ABI 6, additive) sdgpu_identify_files that also returns each file's kind
+ * (mod.rs:59-97 whole), from the bytes the call read for the cas_id: out8,
+ * has_key and status are exactly what sdgpu_identify_files gives; out32 and
+ * has_checksum are either both NULL (no body pass) or exactly what
+ * sdgpu_identify_checksum_files gives.  kind[i] (int32, required) is defined
+ * for rows with status 0 -- empty files included: they are opened and closed
+ * when their name has an Extension, a failure giving kind 0 with status still
+ * 0 -- and 0 for failed rows.  The bytes tested are the bytes that went into
+ * the cas_id, also for a file that changed since its size was taken. */
+int sdgpu_identify_kind_files(sdgpu_ctx *ctx, const char *const *paths, const uint64_t *size,
+                              uint32_t n, uint32_t flags, uint8_t (*out8)[8], uint8_t *has_key,
+                              uint8_t (*out32)[32], uint8_t *has_checksum, int32_t *kind,
+                              int32_t *status);
+
 /* ---- K2/K3: full-file checksum -------------------------------------------------
  * Replaces file_checksum (core/src/object/validation/hash.rs:10-24). */
 /* BLAKE3 of a host buffer. */

@@ -60,6 +60,12 @@ def _proto(L):
         "sdgpu_generate_cas_id": (i32, [ctx, ctypes.c_char_p, u64, ctypes.c_char_p]),
         "sdgpu_identify_files": (i32, [ctx, c_vp, c_vp, u32, c_vp, c_vp, c_vp]),
         "sdgpu_identify_checksum_files": (i32, [ctx, c_vp, c_vp, u32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+        "sdgpu_kind_ext_ids": (i32, [c_vp, u32, c_vp]),
+        "sdgpu_kind_ext_name": (i32, [u32, ctypes.c_char_p, P(ctypes.c_int32)]),
+        "sdgpu_kind_of_file": (i32, [ctypes.c_char_p, u32, P(ctypes.c_int32)]),
+        "sdgpu_kind_batch_device": (i32, [ctx, c_vp, u64, c_vp, c_vp, c_vp, u32, u32, c_vp, c_vp]),
+        "sdgpu_identify_kind_files": (i32, [ctx, c_vp, c_vp, u32, u32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                            c_vp]),
         "sdgpu_checksum": (i32, [ctx, c_vp, u64, c_vp]),
         "sdgpu_checksum_batch_device": (i32, [ctx, c_vp, c_vp, u32, c_vp, c_vp]),
         "sdgpu_subtree_device": (i32, [ctx, c_vp, u64, u64, i32, c_vp, c_vp]),

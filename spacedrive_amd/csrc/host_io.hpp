@@ -323,12 +323,18 @@ struct SlabLayout {
   // with checksums only (0 otherwise): whole flags in, digests and
   // has_checksum out, after the regions every slab has
   size_t whole = 0, sum = 0, has = 0;
+  // with kinds only (0 otherwise): extension ids in (u16 per file), kinds out
+  // (u8 per file), behind everything else
+  size_t ext = 0, kind = 0;
 };
 
 // checksums: the three regions of an identify call that also returns the
 // integrity_checksum of the files it read whole; the other offsets do not
 // depend on it.
-inline SlabLayout slab_layout(size_t arena_cap, uint32_t files_cap, bool checksums = false) {
+// kinds: the two regions of a call that also returns every file's Object kind;
+// no other offset depends on it either.
+inline SlabLayout slab_layout(size_t arena_cap, uint32_t files_cap, bool checksums = false,
+                              bool kinds = false) {
   SlabLayout L;
   L.arena_cap = arena_cap;
   L.files_cap = files_cap;
@@ -342,6 +348,11 @@ inline SlabLayout slab_layout(size_t arena_cap, uint32_t files_cap, bool checksu
     L.sum = align_up(L.whole + 1ull * files_cap, 256);
     L.has = align_up(L.sum + 32ull * files_cap, 256);
     L.total = align_up(L.has + 1ull * files_cap, 256);
+  }
+  if (kinds) {
+    L.ext = L.total;
+    L.kind = align_up(L.ext + 2ull * files_cap, 256);
+    L.total = align_up(L.kind + 1ull * files_cap, 256);
   }
   return L;
 }

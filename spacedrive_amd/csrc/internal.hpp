@@ -72,6 +72,15 @@ hipError_t batch_body_launch(const uint8_t* arena, uint64_t arena_bytes, const u
                              uint32_t max_len, uint8_t* out32, uint8_t* has, const BatchWork& w,
                              hipStream_t s, KTimer* timer = nullptr);
 
+// Object kind of every message (kind.hip, kind_table.hpp): out[i] = the kind of
+// the file whose cas message i is, from its extension id ext[i] (0: none) and
+// the file bytes behind the message's 8-byte prefix; flags: kind::kVerifyMagic.
+// A message batch_hash_launch rejects gets 0.  Reads at most message bytes
+// [0, 48) and no byte at or beyond off[i] + len[i].
+hipError_t kind_launch(const uint8_t* arena, uint64_t arena_bytes, const uint64_t* off,
+                       const uint32_t* len, const uint16_t* ext, uint32_t n, uint32_t max_len,
+                       uint32_t flags, uint8_t* out, hipStream_t s, KTimer* timer = nullptr);
+
 // Latency path for a few messages of at most 1 MiB each (SMALL_MAX_BYTES):
 // ONE launch.  max_chunks = largest chunk count in the batch.  Same status /
 // out semantics as batch_hash_launch.

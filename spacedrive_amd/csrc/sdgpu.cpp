@@ -32,6 +32,7 @@
 #include "host_io.hpp"
 #include "uring.hpp"
 #include "internal.hpp"
+#include "kind_table.hpp"
 #include "scan_device.hpp"
 
 using namespace sdgpu;
@@ -94,7 +95,8 @@ int tree_launch(sdgpu_ctx* c, const TreeSeg* segs, uint32_t nseg, bool cv_input,
 }
 
 int cas_grown_locked(sdgpu_ctx* c, const char* path, uint64_t size, uint8_t out8[8],
-                     uint8_t* out32 = nullptr);
+                     uint8_t* out32 = nullptr, int32_t* kind = nullptr, uint32_t ext = 0,
+                     uint32_t kind_flags = 0);
 
 // ---------------------------------------------------------------------------
 // K1 staging pipeline: slabs of messages packed into pinned memory by a
@@ -106,11 +108,21 @@ int cas_grown_locked(sdgpu_ctx* c, const char* path, uint64_t size, uint8_t out8
 // ---------------------------------------------------------------------------
 
 struct Slab {
-  uint8_t* h = nullptr;  // pinned [arena | off | len | out | status (| whole | sum | has)]
+  uint8_t* h = nullptr;  // pinned [arena | off | len | out | status (| whole | sum | has) (| ext | kind)]
   uint8_t* d = nullptr;  // same layout on the device
   hipEvent_t done = nullptr;
   bool busy = false;
   uint32_t first = 0, count = 0;
+};
+
+// The Object kinds of a pipeline call's files (k_kind once per slab, after K1 on
+// the same stream): ext[i] is row i's extension id, written by the read pool
+// while it handles the row (so before the row's slab is sent); kind[i] receives
+// the kernel's answer when the slab is drained.
+struct KindPass {
+  const uint16_t* ext;
+  uint8_t* kind;
+  uint32_t flags;
 };
 
 // Pinned + device staging slot k of the context (grown on demand, kept).  Only
@@ -133,10 +145,13 @@ int pipe_slot(sdgpu_ctx* c, int k, size_t bytes) {
 // flags out (K1's body pass after the cas pass, every slab on the batch path
 // whatever its file count), and finish takes them as two more arguments.
 // Without it nothing of that is compiled in.
+// kp (optional): the slab also carries the files' extension ids up and their
+// kinds back (KindPass), again on the batch path whatever the file count.
 template <typename Est, typename Produce, typename Finish, typename FillBatch = std::nullptr_t,
           typename Whole = std::nullptr_t>
 int run_pipeline(sdgpu_ctx* c, uint32_t n, Est&& est, Produce&& produce, Finish&& finish,
-                 FillBatch&& fill_batch = nullptr, Whole&& whole = nullptr) {
+                 FillBatch&& fill_batch = nullptr, Whole&& whole = nullptr,
+                 const KindPass* kp = nullptr) {
   (void)pick(c, nullptr);  // runs on the context stream, after earlier work on others
   constexpr int S = sdgpu_ctx::kPipeSlabs;
   constexpr bool kSums = !std::is_same_v<std::decay_t<Whole>, std::nullptr_t>;
@@ -161,7 +176,7 @@ int run_pipeline(sdgpu_ctx* c, uint32_t n, Est&& est, Produce&& produce, Finish&
   const uint64_t target = want <= (kSlabMinBytes << 1) ? want : std::max(want / div, kSlabMinBytes);
   const SlabLayout L = slab_layout(
       static_cast<size_t>(std::clamp<uint64_t>(std::max(target, biggest), 4096, kSlabBytes)),
-      std::clamp<uint32_t>(n, 1, kSlabFiles), kSums);
+      std::clamp<uint32_t>(n, 1, kSlabFiles), kSums, kp != nullptr);
   Slab slabs[S];
   int rc = 0;
   for (int k = 0; k < S && rc == 0; ++k) {
@@ -183,6 +198,7 @@ int run_pipeline(sdgpu_ctx* c, uint32_t n, Est&& est, Produce&& produce, Finish&
     if (hipEventSynchronize(sl.done) != hipSuccess) return -EIO;
     if (ht) ht->host("stage_wait", ms_since(t0));
     sl.busy = false;
+    if (kp) memcpy(kp->kind + sl.first, sl.h + L.kind, sl.count);
     if constexpr (kSums)
       finish(sl.first, sl.count, reinterpret_cast<const uint8_t(*)[8]>(sl.h + L.out),
              reinterpret_cast<const int32_t*>(sl.h + L.status),
@@ -253,7 +269,8 @@ int run_pipeline(sdgpu_ctx* c, uint32_t n, Est&& est, Produce&& produce, Finish&
     for (uint32_t j = 0; j < cnt; ++j) max_msg = std::max(max_msg, len[j]);
     if constexpr (kSums)
       for (uint32_t j = 0; j < cnt; ++j) hb[L.whole + j] = whole(sl.first + j) ? 1 : 0;
-    const bool small = !kSums && cnt <= kSmallBatch && max_msg <= SMALL_MAX_BYTES;
+    if (kp) memcpy(hb + L.ext, kp->ext + sl.first, 2ull * cnt);
+    const bool small = !kSums && !kp && cnt <= kSmallBatch && max_msg <= SMALL_MAX_BYTES;
     const size_t prefix = L.len + 4ull * cnt;
     // a few cas messages (the single-file and small-batch callers): read from
     // the pinned slab and the ids written back into it by the kernel itself,
@@ -288,6 +305,13 @@ int run_pipeline(sdgpu_ctx* c, uint32_t n, Est&& est, Produce&& produce, Finish&
            hipMemcpyAsync(hb + L.sum, db + L.sum, 32ull * cnt, hipMemcpyDeviceToHost, s) ==
                hipSuccess &&
            hipMemcpyAsync(hb + L.has, db + L.has, cnt, hipMemcpyDeviceToHost, s) == hipSuccess;
+    if (kp)  // the kinds, from the message heads K1 has just hashed
+      ok = ok &&
+           hipMemcpyAsync(db + L.ext, hb + L.ext, 2ull * cnt, hipMemcpyHostToDevice, s) ==
+               hipSuccess &&
+           kind_launch(db, L.arena_cap, d_off, d_len, reinterpret_cast<const uint16_t*>(db + L.ext),
+                       cnt, kStageMaxMsg, kp->flags, db + L.kind, s, c->kt()) == hipSuccess &&
+           hipMemcpyAsync(hb + L.kind, db + L.kind, cnt, hipMemcpyDeviceToHost, s) == hipSuccess;
     if (!ok ||
         (!host1 &&
          hipMemcpyAsync(hb + L.out, db + L.out, 8ull * cnt, hipMemcpyDeviceToHost, s) != hipSuccess) ||
@@ -488,6 +512,22 @@ int sdgpu_cas_checksum_batch_device(sdgpu_ctx* c, const uint8_t* d_arena, uint64
   return 0;
 }
 
+int sdgpu_kind_batch_device(sdgpu_ctx* c, const uint8_t* d_arena, uint64_t arena_bytes,
+                            const uint64_t* d_off, const uint32_t* d_len, const uint16_t* d_ext,
+                            uint32_t n, uint32_t flags, uint8_t* d_kind, void* stream) {
+  if (!c || (flags & ~SDGPU_KIND_VERIFY_MAGIC) ||
+      (n && (!d_arena || !d_off || !d_len || !d_ext || !d_kind)))
+    return -EINVAL;
+  if (reinterpret_cast<uintptr_t>(d_arena) % 16 || reinterpret_cast<uintptr_t>(d_ext) % 2)
+    return -EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  SD_TRY(hipSetDevice(c->device));
+  hipStream_t s = pick(c, stream);
+  SD_TRY(kind_launch(d_arena, arena_bytes, d_off, d_len, d_ext, n, CAS_MAX_MSG_LEN, flags, d_kind, s,
+                     c->kt()));
+  return 0;
+}
+
 // Pinned-host staged K1 (config 5): slabs of the caller's pinned arena are
 // copied H2D on the context's copy stream (SDMA) into a ring of three device
 // slabs while K1 hashes the previous slab on the compute stream; events order
@@ -618,14 +658,22 @@ int sdgpu_cas_batch(sdgpu_ctx* c, const uint8_t* msg_arena, const uint64_t* msg_
 extern "C++" {
 namespace {
 
-// sdgpu_identify_files (kSums false: out32 / has_checksum unused) and
-// sdgpu_identify_checksum_files (kSums true) -- one body, so the reads, the
-// statuses and the cas ids of the two cannot drift apart; the checksum parts
-// are compiled into the second only.
+// What sdgpu_identify_kind_files adds to an identify call.
+struct KindReq {
+  uint32_t flags;
+  int32_t* kind;  // [n]
+};
+
+// sdgpu_identify_files (kSums false: out32 / has_checksum unused),
+// sdgpu_identify_checksum_files (kSums true) and sdgpu_identify_kind_files
+// (either, with kr) -- one body, so the reads, the statuses and the cas ids of
+// the three cannot drift apart; the checksum parts are compiled into kSums
+// only, and without kr no kind work is done.
 template <bool kSums>
 int identify_files_locked(sdgpu_ctx* c, const char* const* paths, const uint64_t* size_in,
                           uint32_t n, uint8_t (*out8)[8], uint8_t* has_key, int32_t* status,
-                          uint8_t (*out32)[32], uint8_t* has_checksum) {
+                          uint8_t (*out32)[32], uint8_t* has_checksum,
+                          const KindReq* kr = nullptr) {
   // size NULL (ABI 6): the fresh fs::metadata(path).len() of the reference
   // (file_identifier/mod.rs:65,80-81), stat-ed here by the read pool; a path
   // whose stat fails gets status -errno and no key (the row is dropped,
@@ -647,12 +695,39 @@ int identify_files_locked(sdgpu_ctx* c, const char* const* paths, const uint64_t
   const uint64_t* size = size_in ? size_in : fresh.data();
   auto failed = [&](uint32_t i) -> int32_t { return stat_rc.empty() ? 0 : stat_rc[i]; };
   std::vector<uint32_t> grown;  // <= 100 KiB at stat, longer than its room at read
+  // kinds: the pool thread that handles a row resolves its extension id
+  // (magic.rs:180-186).  A non-empty file is opened by its cas read; an empty
+  // one is not read, so when its name has an Extension it is opened and closed
+  // here, and a failure leaves it without one (kind 0, magic.rs:188-190) --
+  // the status stays 0.
+  std::vector<uint16_t> ext;
+  std::vector<uint8_t> kind8;
+  std::vector<int32_t> own_status;
+  if (kr) {
+    ext.assign(n, 0);
+    kind8.assign(n, 0);
+    if (!status) {
+      own_status.assign(n, 0);
+      status = own_status.data();
+    }
+  }
+  auto note_ext = [&](uint32_t i) {
+    if (!kr || failed(i)) return;
+    uint16_t e = kind::ext_id_of_path(paths[i]);
+    if (e && size[i] == 0) {
+      const int fd = open(paths[i], O_RDONLY | O_CLOEXEC);
+      if (fd < 0) e = 0;
+      else close(fd);
+    }
+    ext[i] = e;
+  };
   auto est = [&](uint32_t i) -> uint64_t {
     if (size[i] == 0 || failed(i)) return 16;
     return size[i] <= SDGPU_CAS_MINIMUM_FILE_SIZE ? 8 + size[i] + 4096  // room to grow
                                                   : SDGPU_CAS_SAMPLED_MSG_LEN;
   };
   auto produce = [&](uint32_t i, uint8_t* dst, size_t cap) -> int64_t {
+    note_ext(i);
     if (failed(i)) return failed(i);
     if (size[i] == 0) return 0x7fffffff;  // cas_id None (file_identifier/mod.rs:80-88)
     if (c->io_bounce) return read_cas_message_bounce(paths[i], size[i], dst, cap);
@@ -699,6 +774,7 @@ int identify_files_locked(sdgpu_ctx* c, const char* const* paths, const uint64_t
           uint32_t idx[kGrain], m = 0;
           for (uint32_t j = j0; j < j1; ++j) {
             const uint32_t i = first + j;
+            note_ext(i);
             if (failed(i)) {
               settle(j, failed(i));
               continue;
@@ -725,13 +801,19 @@ int identify_files_locked(sdgpu_ctx* c, const char* const* paths, const uint64_t
   (void)finish_sums;
   (void)whole;
   int rc;
-  if constexpr (kSums) rc = run_pipeline(c, n, est, produce, finish_sums, fill_uring, whole);
-  else rc = run_pipeline(c, n, est, produce, finish, fill_uring);
+  const KindPass pass{ext.data(), kind8.data(), kr ? kr->flags : 0};
+  const KindPass* kp = kr ? &pass : nullptr;
+  if constexpr (kSums) rc = run_pipeline(c, n, est, produce, finish_sums, fill_uring, whole, kp);
+  else rc = run_pipeline(c, n, est, produce, finish, fill_uring, nullptr, kp);
   if (rc) return rc;
+  if (kr)  // failed rows (a grown one until it is re-read below) have no kind
+    for (uint32_t i = 0; i < n; ++i) kr->kind[i] = status[i] == 0 ? kind8[i] : 0;
   for (const uint32_t i : grown) {
     // the buffer cas_grown_locked reads is hashed a second time without its
-    // prefix: no second read of the file
-    const int r = cas_grown_locked(c, paths[i], size[i], out8[i], kSums ? out32[i] : nullptr);
+    // prefix, and its head gives the kind: no second read of the file
+    const int r = cas_grown_locked(c, paths[i], size[i], out8[i], kSums ? out32[i] : nullptr,
+                                   kr ? &kr->kind[i] : nullptr, kr ? ext[i] : 0,
+                                   kr ? kr->flags : 0);
     if (r) memset(out8[i], 0, 8);
     if (has_key) has_key[i] = r == 0 ? 1 : 0;
     if (status) status[i] = r;
@@ -762,6 +844,22 @@ int sdgpu_identify_checksum_files(sdgpu_ctx* c, const char* const* paths, const 
   SD_TRY(hipSetDevice(c->device));
   return identify_files_locked<true>(c, paths, size_in, n, out8, has_key, status, out32,
                                      has_checksum);
+}
+
+int sdgpu_identify_kind_files(sdgpu_ctx* c, const char* const* paths, const uint64_t* size_in,
+                              uint32_t n, uint32_t flags, uint8_t (*out8)[8], uint8_t* has_key,
+                              uint8_t (*out32)[32], uint8_t* has_checksum, int32_t* kind,
+                              int32_t* status) {
+  if (!c || (flags & ~SDGPU_KIND_VERIFY_MAGIC) || (n && (!paths || !out8 || !kind))) return -EINVAL;
+  if ((out32 == nullptr) != (has_checksum == nullptr)) return -EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  SD_TRY(hipSetDevice(c->device));
+  const KindReq kr{flags, kind};
+  if (out32)
+    return identify_files_locked<true>(c, paths, size_in, n, out8, has_key, status, out32,
+                                       has_checksum, &kr);
+  return identify_files_locked<false>(c, paths, size_in, n, out8, has_key, status, nullptr, nullptr,
+                                      &kr);
 }
 
 // ---- the resident latency service (f3) ----------------------------------------
@@ -982,7 +1080,7 @@ int checksum_host_locked(sdgpu_ctx* c, const void* bytes, uint64_t len, uint8_t 
 // out32 (optional): also BLAKE3 of that content alone, the file's
 // integrity_checksum at the moment of the read, from the same buffer.
 int cas_grown_locked(sdgpu_ctx* c, const char* path, uint64_t size, uint8_t out8[8],
-                     uint8_t* out32) {
+                     uint8_t* out32, int32_t* kind, uint32_t ext, uint32_t kind_flags) {
   const int fd = open(path, O_RDONLY | O_CLOEXEC);
   if (fd < 0) return -errno;
   std::vector<uint8_t> msg(8);
@@ -1006,6 +1104,8 @@ int cas_grown_locked(sdgpu_ctx* c, const char* path, uint64_t size, uint8_t out8
   SD_TRY_RC(checksum_host_locked(c, msg.data(), msg.size(), d));
   if (out32) SD_TRY_RC(checksum_host_locked(c, msg.data() + 8, msg.size() - 8, out32));
   memcpy(out8, d, 8);
+  // the host side of the one matcher (kind_table.hpp), on the bytes just hashed
+  if (kind) *kind = kind::kind_of_bytes(ext, msg.data() + 8, msg.size() - 8, kind_flags);
   return 0;
 }
 

@@ -1,9 +1,9 @@
 """File identifier -- host mirror of core/src/object/file_identifier/mod.rs.
 
 * ``FileMetadata`` / ``file_metadata(location_path, iso_path)``  (mod.rs:50-97):
-  stat, refuse directories, cas_id None for empty files, else generate_cas_id.
-  (`kind` -- sd-file-ext magic-byte sniffing, mod.rs:75-78 -- is outside the
-  hot path and stays ObjectKind::Unknown = 0 here.)
+  stat, refuse directories, cas_id None for empty files, else generate_cas_id;
+  `kind` is Extension::resolve_conflicting(&path, false) (mod.rs:75-78,
+  ``kind.kind_of_file``).
 * ``identify(paths)``: the batched form of identifier_job_step's metadata
   phase (mod.rs:107-134) -- every file's cas windows are pread into pinned
   slabs and hashed by K1 while the next slab is read (sdgpu_identify_files).
@@ -11,6 +11,10 @@
   every file read whole (sdgpu_identify_checksum_files), so the object
   validator (validator_job.rs:100-169) is left with the sampled and the
   empty files.
+* ``identify_metadata(paths)``: ``identify`` that also returns every file's
+  Object kind (mod.rs:75-78) from the bytes the same read staged on the
+  device (sdgpu_identify_kind_files, k_kind): all three outputs of
+  FileMetadata::new from one call.
 * ``identifier_job(paths)``: the whole job over orphan rows in id order --
   cas ids, then the Object grouping of every row (dedup.group_reps), with the
   reference's per-step (created, linked) accounting.
@@ -32,6 +36,7 @@ import numpy as np
 
 from . import cas as _cas
 from . import dedup as _dedup
+from . import kind as _kind
 from ._native import SdgpuError, check, default_context
 
 CHUNK_SIZE = 100  # mod.rs:36
@@ -50,7 +55,7 @@ def file_metadata(location_path, iso_file_path, ctx=None) -> FileMetadata:
     st = os.stat(path)
     assert not _stat.S_ISDIR(st.st_mode), "We can't generate cas_id for directories"
     cas_id = _cas.generate_cas_id(path, st.st_size, ctx) if st.st_size != 0 else None
-    return FileMetadata(cas_id=cas_id, kind=0, size=st.st_size)
+    return FileMetadata(cas_id=cas_id, kind=int(_kind.kind_of_file(path)), size=st.st_size)
 
 
 @dataclass
@@ -61,6 +66,7 @@ class IdentifyResult:
     sizes: np.ndarray | None  # [n] uint64 as passed; None: stat-ed by the library
     checksum32: np.ndarray | None = None    # [n, 32] uint8 (identify(checksums=True))
     has_checksum: np.ndarray | None = None  # [n] uint8: 1 = the file was read whole
+    kind: np.ndarray | None = None          # [n] int32 ObjectKind (identify_metadata)
 
     def cas_ids(self) -> list[str | None]:
         return [bytes(self.cas8[i]).hex() if self.has_key[i] else None
@@ -72,6 +78,15 @@ class IdentifyResult:
             return [None] * self.has_key.size
         return [bytes(self.checksum32[i]).hex() if self.has_checksum[i] else None
                 for i in range(self.has_checksum.size)]
+
+
+    def kinds(self) -> list["_kind.ObjectKind | None"]:
+        """ObjectKind of the rows with status 0, else None (and None for every
+        row when the call did not ask for kinds)."""
+        if self.kind is None:
+            return [None] * self.has_key.size
+        return [_kind.ObjectKind(int(self.kind[i])) if self.status[i] == 0 else None
+                for i in range(self.kind.size)]
 
 
 class PathList:
@@ -125,6 +140,33 @@ def identify(paths, sizes=None, ctx=None, checksums: bool = False) -> IdentifyRe
     return IdentifyResult(out, has, status, sizes)
 
 
+def identify_metadata(paths, sizes=None, ctx=None, checksums: bool = False,
+                      verify_magic: bool = False) -> IdentifyResult:
+    """``identify`` plus the Object kind of every file (mod.rs:75-78), decided
+    on the device from the bytes the call read for the cas_id -- no second
+    open per file.  cas8, has_key, status (and, with checksums, checksum32 and
+    has_checksum) are exactly ``identify``'s.  kind is defined for rows with
+    status 0, empty files included; failed rows get 0.  verify_magic:
+    resolve_conflicting's always_check_magic_bytes (off in the identifier)."""
+    ctx = ctx or default_context()
+    n = len(paths)
+    if sizes is not None:
+        sizes = np.ascontiguousarray(sizes, np.uint64)
+    arr = paths.c_paths if isinstance(paths, PathList) else PathList(paths).c_paths
+    out = np.zeros((n, 8), np.uint8)
+    has = np.zeros(n, np.uint8)
+    status = np.zeros(n, np.int32)
+    kind = np.zeros(n, np.int32)
+    out32 = np.zeros((n, 32), np.uint8) if checksums else None
+    has32 = np.zeros(n, np.uint8) if checksums else None
+    check(ctx.lib.sdgpu_identify_kind_files(
+        ctx.h, arr, sizes.ctypes.data if sizes is not None else None, n,
+        _kind.VERIFY_MAGIC if verify_magic else 0, out.ctypes.data, has.ctypes.data,
+        out32.ctypes.data if checksums else None, has32.ctypes.data if checksums else None,
+        kind.ctypes.data, status.ctypes.data), "sdgpu_identify_kind_files")
+    return IdentifyResult(out, has, status, sizes, out32, has32, kind)
+
+
 @dataclass
 class JobResult:
     identify: IdentifyResult
@@ -164,6 +206,9 @@ class FilePaths:
         self.cas_id: list[str | None] = []
         self.object_id: list[int | None] = []
         self.integrity_checksum: list[str | None] = []
+        # object.kind of the Objects a job with kinds=True created
+        # (mod.rs:256-275, object::kind::set): Object id -> ObjectKind value
+        self.object_kind: dict[int, int] = {}
         self.next_object_id = 1
         # per location, the ids of its non-directory rows (ascending: ids are
         # appended in order) -- the index the orphan query walks from the cursor
@@ -328,13 +373,19 @@ class FileIdentifierJob:
     checksums: every step also writes the integrity_checksum of the rows whose
     file it read whole (identify(checksums=True)); the validator that follows
     (its paths: FilePaths.unvalidated) then only has the sampled and the empty
-    files left."""
+    files left.
+
+    kinds: every step identifies through identify_metadata, and a row that
+    creates an Object records the Object's kind (FilePaths.object_kind,
+    mod.rs:256-275); a row linked to an existing Object changes nothing."""
 
     def __init__(self, table: FilePaths, location_id: int, location_path: str,
                  sub_path: str | None = None, chunks_per_step: int = 64, ctx=None,
-                 _shallow_dir: str | None = None, index=None, checksums: bool = False):
+                 _shallow_dir: str | None = None, index=None, checksums: bool = False,
+                 kinds: bool = False):
         self.table = table
         self.checksums = bool(checksums)
+        self.kinds = bool(kinds)
         self.location_id = location_id
         self.location_path = location_path
         self.sub_path = sub_path
@@ -399,7 +450,10 @@ class FileIdentifierJob:
         if not cand:
             raise EarlyFinish("Expected orphan Paths not returned from database query for this chunk")
         paths = [os.path.join(self.location_path, self.table.rel_path(f)) for f in cand]
-        ident = identify(paths, ctx=self.ctx, checksums=self.checksums)
+        if self.kinds:
+            ident = identify_metadata(paths, ctx=self.ctx, checksums=self.checksums)
+        else:
+            ident = identify(paths, ctx=self.ctx, checksums=self.checksums)
         ok = {f: ident.status[i] == 0 for i, f in enumerate(cand)}
         pos = {f: i for i, f in enumerate(cand)}
         # replay the reference's fetches: chunk c = the next 100 orphans with
@@ -445,6 +499,8 @@ class FileIdentifierJob:
                 t.next_object_id += 1
                 self._creator_object[r] = obj
                 created += 1
+                if self.kinds:
+                    t.object_kind[obj] = int(ident.kind[pos[f]])
                 if has[j]:
                     new_keys.append(key[j])
                     new_objs.append(obj)
@@ -482,13 +538,13 @@ class FileIdentifierJob:
                 "sub_path": self.sub_path, "shallow_dir": self._children_of,
                 "chunks_per_step": self.chunks_per_step, "step_number": self.step_number,
                 "task_count": self.task_count, "run_metadata": asdict(self.meta),
-                "checksums": self.checksums}
+                "checksums": self.checksums, "kinds": self.kinds}
 
     @classmethod
     def resume(cls, table: FilePaths, state: dict, ctx=None, index=None) -> "FileIdentifierJob":
         job = cls(table, state["location_id"], state["location_path"], state["sub_path"],
                   state["chunks_per_step"], ctx, state.get("shallow_dir"), index=index,
-                  checksums=state.get("checksums", False))
+                  checksums=state.get("checksums", False), kinds=state.get("kinds", False))
         job.meta = IdentifierRunMetadata(**state["run_metadata"])
         job.step_number = state["step_number"]
         job.task_count = state["task_count"]
@@ -506,14 +562,15 @@ class EarlyFinish(Exception):
 
 
 def shallow(table: FilePaths, location_id: int, location_path: str, sub_path: str = "",
-            chunks_per_step: int = 64, ctx=None, checksums: bool = False) -> IdentifierRunMetadata:
+            chunks_per_step: int = 64, ctx=None, checksums: bool = False,
+            kinds: bool = False) -> IdentifierRunMetadata:
     """file_identifier::shallow (shallow.rs:26-119): the light scan of one
     directory -- only its direct children (materialized_path equal to the
     directory's children path, :121-139), all steps at once, outside the job
     system; no orphans is not an error (:65-67)."""
     d = "/" + sub_path.strip("/") + "/" if sub_path.strip("/") else "/"
     job = FileIdentifierJob(table, location_id, location_path, None, chunks_per_step, ctx,
-                            _shallow_dir=d, checksums=checksums)
+                            _shallow_dir=d, checksums=checksums, kinds=kinds)
     try:
         job.init()
     except EarlyFinish:
@@ -524,6 +581,6 @@ def shallow(table: FilePaths, location_id: int, location_path: str, sub_path: st
         job.close()
 
 
-__all__ = ["FileMetadata", "file_metadata", "identify", "identifier_job", "IdentifyResult",
+__all__ = ["FileMetadata", "file_metadata", "identify", "identify_metadata", "identifier_job", "IdentifyResult",
            "JobResult", "SdgpuError", "FilePaths", "FileIdentifierJob", "IdentifierRunMetadata",
            "EarlyFinish", "shallow"]
