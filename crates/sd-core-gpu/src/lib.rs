@@ -5,6 +5,8 @@
 //! * `file_checksum(path)`         -- core/src/object/validation/hash.rs:10 (`hash.rs` here)
 //! * the grouping / write set of `identifier_job_step`
 //!   -- core/src/object/file_identifier/mod.rs:100-336 (`identifier.rs` here)
+//! * the stale-thumbnail sweep `process_clean_up`
+//!   -- core/src/object/thumbnail_remover.rs:236-367 (`thumbnail_remover.rs` here)
 //!
 //! Blocking library calls run inside `spawn_blocking`, as the reference's
 //! `tokio::fs` calls do, so the async runtime never blocks.  Errors are the
@@ -19,6 +21,7 @@ pub mod cas;
 pub mod hash;
 pub mod identifier;
 pub mod job;
+pub mod thumbnail_remover;
 
 use std::{
     ffi::{CStr, CString},

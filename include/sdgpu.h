@@ -689,6 +689,41 @@ int sdgpu_orphan_objects_device(sdgpu_ctx *ctx, const int32_t *d_object_ids, uin
  * d_counts[256] = rows per directory. */
 int sdgpu_thumbnail_shards_device(sdgpu_ctx *ctx, const uint8_t *d_cas8, const uint8_t *d_valid,
                                   uint64_t n, uint32_t *d_order, uint32_t *d_counts, void *stream);
+/* (ABI 6, additive) Thumbnail remover (core/src/object/thumbnail_remover.rs:
+ * 236-367, process_clean_up): which thumbnails on disk does no file_path own
+ * any more.  The thumbnails are listed directory by directory: d_thumb_key
+ * [n_thumbs] are their cas keys, d_dir_start[0..n_dirs] ascending offsets
+ * (directory d owns [start[d], start[d+1]); empty directories are allowed;
+ * start[0] = 0, start[n_dirs] = n_thumbs).  The file_paths are n_cols <= 64
+ * columns: d_col_key, d_col_has_key and col_rows are HOST arrays of n_cols
+ * device pointers / row counts; any col_rows[c] may be 0, d_col_has_key (or
+ * any entry of it) may be NULL = every row keyed; a row with has_key == 0
+ * owns nothing whatever its key bytes hold.  The set of non-indexed
+ * thumbnails is one more column.  d_stale (capacity n_thumbs) receives the
+ * positions in the thumbnail list of those no row owns, in list order;
+ * d_stale_start[0..n_dirs] their per-directory offsets, d_stale_start[n_dirs]
+ * the total: directory d is emptied iff its stale count equals its size.  The
+ * same key listed twice gets one answer.  n_thumbs < 2^31 (the table of
+ * thumbnail keys in the context's workspace has 2 x n_thumbs slots rounded up
+ * to a power of two, 2^31 at the most); -EINVAL on NULL or inconsistent
+ * arguments.  Asynchronous on `stream`, no synchronisation.
+ * One GPU: a sharded library runs the call on every share's columns and ORs
+ * the answers (a thumbnail is stale when it is stale on every share). */
+int sdgpu_stale_thumbnails_device(sdgpu_ctx *ctx, const uint64_t *d_thumb_key, uint64_t n_thumbs,
+                                  const uint32_t *d_dir_start, uint32_t n_dirs,
+                                  const uint64_t *const *d_col_key,
+                                  const uint8_t *const *d_col_has_key, const uint64_t *col_rows,
+                                  uint32_t n_cols, uint32_t *d_stale, uint32_t *d_stale_start,
+                                  void *stream);
+/* (ABI 6, additive) The same on host arrays (what the Rust actor calls with the
+ * columns it fetched from the databases; col_key / col_has_key hold host
+ * pointers): copy in, run, copy out; returns when done.  dir_start is checked
+ * (-EINVAL unless it ascends from 0 to n_thumbs). */
+int sdgpu_stale_thumbnails(sdgpu_ctx *ctx, const uint64_t *thumb_key, uint64_t n_thumbs,
+                           const uint32_t *dir_start, uint32_t n_dirs,
+                           const uint64_t *const *col_key, const uint8_t *const *col_has_key,
+                           const uint64_t *col_rows, uint32_t n_cols, uint32_t *stale,
+                           uint32_t *stale_start);
 
 /* ---- synthetic corpora (bench / tests; same content function as oracle/) ---- */
 int sdgpu_synth_cas_arena_device(sdgpu_ctx *ctx, const uint64_t *d_sizes, const uint64_t *d_seeds,

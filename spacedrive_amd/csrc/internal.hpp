@@ -361,6 +361,18 @@ size_t thumb_workspace_bytes();
 hipError_t thumbnail_shards_launch(const uint8_t* cas8, const uint8_t* valid, uint64_t n,
                                    uint32_t* order, uint32_t* counts, void* ws, hipStream_t s);
 
+// ---- thumbnail remover (thumbnail_remover.hip) ------------------------------------
+// One call = build, a probe per file_path column (any number, no host
+// synchronisation between them), compact; all three address the same ws of
+// stale_workspace_bytes(n_thumbs) bytes.  col_has may be null (every row keyed).
+size_t stale_workspace_bytes(uint64_t n_thumbs);
+hipError_t stale_build_launch(const uint64_t* thumb_key, uint64_t n_thumbs, void* ws,
+                              hipStream_t s);
+hipError_t stale_probe_launch(uint64_t n_thumbs, const uint64_t* col_key, const uint8_t* col_has,
+                              uint64_t rows, void* ws, hipStream_t s);
+hipError_t stale_compact_launch(uint64_t n_thumbs, const uint32_t* dir_start, uint32_t n_dirs,
+                                uint32_t* stale, uint32_t* stale_start, void* ws, hipStream_t s);
+
 // ---- Object link batch (K7) ----------------------------------------------------
 size_t link_workspace_bytes(uint64_t n);
 // rank may be null (rank = first_rank + i), valid may be null (all rows valid).

@@ -1611,6 +1611,107 @@ int sdgpu_thumbnail_shards_device(sdgpu_ctx* c, const uint8_t* d_cas8, const uin
   return 0;
 }
 
+// Thumbnail remover (thumbnail_remover.hip).  The checks both variants share:
+// everything that can be told from the host arguments alone.
+static bool stale_args_ok(sdgpu_ctx* c, const uint64_t* thumb_key, uint64_t n_thumbs,
+                          const uint32_t* dir_start, uint32_t n_dirs,
+                          const uint64_t* const* col_key, const uint64_t* col_rows,
+                          uint32_t n_cols, const uint32_t* stale, const uint32_t* stale_start) {
+  if (!c || !dir_start || !stale_start || n_thumbs >= (1ull << 31) || n_cols > 64) return false;
+  if (n_thumbs && (!thumb_key || !stale || n_dirs == 0)) return false;
+  if (n_cols && (!col_key || !col_rows)) return false;
+  for (uint32_t i = 0; i < n_cols; ++i)
+    if (col_rows[i] && !col_key[i]) return false;
+  return true;
+}
+
+int sdgpu_stale_thumbnails_device(sdgpu_ctx* c, const uint64_t* d_thumb_key, uint64_t n_thumbs,
+                                  const uint32_t* d_dir_start, uint32_t n_dirs,
+                                  const uint64_t* const* d_col_key,
+                                  const uint8_t* const* d_col_has_key, const uint64_t* col_rows,
+                                  uint32_t n_cols, uint32_t* d_stale, uint32_t* d_stale_start,
+                                  void* stream) {
+  if (!stale_args_ok(c, d_thumb_key, n_thumbs, d_dir_start, n_dirs, d_col_key, col_rows, n_cols,
+                     d_stale, d_stale_start))
+    return -EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  SD_TRY(hipSetDevice(c->device));
+  hipStream_t s = pick(c, stream);
+  SD_TRY_RC(ensure_dev(c, c->link_ws, stale_workspace_bytes(n_thumbs)));
+  void* ws = c->link_ws.p;
+  if (n_thumbs) {  // no thumbnails: nothing to build or probe, the offsets are all 0
+    SD_TRY(stale_build_launch(d_thumb_key, n_thumbs, ws, s));
+    for (uint32_t i = 0; i < n_cols; ++i)
+      SD_TRY(stale_probe_launch(n_thumbs, d_col_key[i], d_col_has_key ? d_col_has_key[i] : nullptr,
+                                col_rows[i], ws, s));
+  }
+  SD_TRY(stale_compact_launch(n_thumbs, d_dir_start, n_dirs, d_stale, d_stale_start, ws, s));
+  return 0;
+}
+
+int sdgpu_stale_thumbnails(sdgpu_ctx* c, const uint64_t* thumb_key, uint64_t n_thumbs,
+                           const uint32_t* dir_start, uint32_t n_dirs,
+                           const uint64_t* const* col_key, const uint8_t* const* col_has_key,
+                           const uint64_t* col_rows, uint32_t n_cols, uint32_t* stale,
+                           uint32_t* stale_start) {
+  if (!stale_args_ok(c, thumb_key, n_thumbs, dir_start, n_dirs, col_key, col_rows, n_cols, stale,
+                     stale_start))
+    return -EINVAL;
+  // host arrays can be read: the directory offsets ascend from 0 to n_thumbs
+  if (dir_start[0] != 0 || dir_start[n_dirs] != n_thumbs) return -EINVAL;
+  for (uint32_t d = 0; d < n_dirs; ++d)
+    if (dir_start[d] > dir_start[d + 1]) return -EINVAL;
+  const size_t bounds = static_cast<size_t>(n_dirs) + 1;
+  if (n_thumbs == 0) {
+    memset(stale_start, 0, 4 * bounds);
+    return 0;
+  }
+  std::lock_guard<std::mutex> g(c->mu);
+  SD_TRY(hipSetDevice(c->device));
+  hipStream_t s = pick(c, nullptr);
+  // workspace | thumbnail keys | dir_start | stale | stale_start | one piece of
+  // a column (keys, has_key) in the context's link workspace: a column of any
+  // length is copied in and probed kPiece rows at a time (the copy of the next
+  // piece is ordered after the probe of this one by the stream)
+  constexpr uint64_t kPiece = 1ull << 23;
+  uint64_t piece = 0;
+  for (uint32_t i = 0; i < n_cols; ++i) piece = std::max(piece, std::min(col_rows[i], kPiece));
+  const size_t o_key = align_up(stale_workspace_bytes(n_thumbs), 256);
+  const size_t o_dir = o_key + align_up(8 * n_thumbs, 256);
+  const size_t o_out = o_dir + align_up(4 * bounds, 256);
+  const size_t o_start = o_out + align_up(4 * n_thumbs, 256);
+  const size_t o_ck = o_start + align_up(4 * bounds, 256);
+  const size_t o_ch = o_ck + align_up(8 * piece, 256);
+  SD_TRY_RC(ensure_dev(c, c->link_ws, o_ch + piece));
+  uint8_t* base = static_cast<uint8_t*>(c->link_ws.p);
+  uint64_t* dk = reinterpret_cast<uint64_t*>(base + o_key);
+  uint32_t* dd = reinterpret_cast<uint32_t*>(base + o_dir);
+  uint32_t* dout = reinterpret_cast<uint32_t*>(base + o_out);
+  uint32_t* dstart = reinterpret_cast<uint32_t*>(base + o_start);
+  uint64_t* ck = reinterpret_cast<uint64_t*>(base + o_ck);
+  uint8_t* ch = base + o_ch;
+  SD_TRY(hipMemcpyAsync(dk, thumb_key, 8 * n_thumbs, hipMemcpyHostToDevice, s));
+  SD_TRY(hipMemcpyAsync(dd, dir_start, 4 * bounds, hipMemcpyHostToDevice, s));
+  SD_TRY(stale_build_launch(dk, n_thumbs, base, s));
+  for (uint32_t i = 0; i < n_cols; ++i) {
+    const uint8_t* has = col_has_key ? col_has_key[i] : nullptr;
+    for (uint64_t r0 = 0; r0 < col_rows[i]; r0 += kPiece) {
+      const uint64_t r = std::min(kPiece, col_rows[i] - r0);
+      SD_TRY(hipMemcpyAsync(ck, col_key[i] + r0, 8 * r, hipMemcpyHostToDevice, s));
+      if (has) SD_TRY(hipMemcpyAsync(ch, has + r0, r, hipMemcpyHostToDevice, s));
+      SD_TRY(stale_probe_launch(n_thumbs, ck, has ? ch : nullptr, r, base, s));
+    }
+  }
+  SD_TRY(stale_compact_launch(n_thumbs, dd, n_dirs, dout, dstart, base, s));
+  SD_TRY(hipMemcpyAsync(stale_start, dstart, 4 * bounds, hipMemcpyDeviceToHost, s));
+  SD_TRY(hipStreamSynchronize(s));
+  // only the stale positions travel back
+  if (stale_start[n_dirs])
+    SD_TRY(hipMemcpy(stale, dout, 4 * static_cast<size_t>(stale_start[n_dirs]),
+                     hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int sdgpu_synth_vary_keys_device(sdgpu_ctx* c, uint64_t* d_key, const uint8_t* d_vary,
                                  uint64_t n, uint64_t step, void* stream) {
   if (!c || (n && (!d_key || !d_vary))) return -EINVAL;

@@ -1,0 +1,333 @@
+// Thumbnail remover: the stale-thumbnail sweep as one device
+// anti-join.
+//
+// Reference: core/src/object/thumbnail_remover.rs:236-367 (process_clean_up).
+// Every half hour, for every shard directory of the thumbnail cache, it asks
+// every loaded library `file_path.cas_id IN (the directory's <cas_id>.webp
+// stems)` -- a full table scan per directory and library, the schema has no
+// index on cas_id -- drops the stems the in-memory set of non-indexed
+// thumbnails holds, unlinks the rest, and removes a directory when everything
+// it found there went.
+//
+// Here the table is built on the SMALL side: the thumbnail keys go into an
+// open-addressing table in the context's workspace (8-byte slots, capacity a
+// power of two >= 2 x n_thumbs, linear probing from row_hash(key), empty slot
+// ~0; the key ~0 itself owns the slot one past the table, as index.hip does
+// it), every thumbnail remembers the slot it ended in (slot_of), and the LARGE
+// side -- the cas key columns of the file_paths, plus the non-indexed set as
+// one more column -- is streamed once: a row whose key sits in the table
+// stores hit[slot] = 1, a plain byte store (idempotent: no atomics in that
+// pass); a one-bit-per-hash filter in front of the table keeps most rows that
+// own no thumbnail out of it (k_stale_probe).  The thumbnails whose slot was not hit are then compacted in list
+// order (4096-row tiles: count, one scan of the tile counts, in-tile ballot
+// ranks -- k_orphan_count / k_orphan_write's scheme), and every directory
+// boundary gets its offset into that list from its tile's offset plus a count
+// of the tile's rows before it.  A key listed twice (a misplaced copy in a
+// second directory) ends in one slot, so both copies get one answer.
+#include "internal.hpp"
+#include "rows_device.hpp"
+#include "scan_device.hpp"
+
+namespace sdgpu {
+
+namespace {
+
+constexpr uint64_t kEmptyKey = ~0ull;
+constexpr int kThreads = 256;
+constexpr uint64_t kMinCap = 1024;
+
+struct StaleWs {
+  uint64_t cap;       // slots; the key ~0 owns slot `cap`
+  uint64_t* table;    // [cap]
+  uint8_t* hit;       // [cap + 1]
+  uint32_t* bits;     // [cap / 4] the probe's filter: a bit per thumbnail key's hash
+  uint32_t* slot_of;  // [n]
+  uint32_t* cnt;      // [blocks + 1] stale per tile, then their offsets
+  uint32_t* tiles;    // scan::exclusive's tile sums
+  size_t bytes;
+};
+
+uint64_t stale_cap(uint64_t n) {
+  uint64_t cap = kMinCap;
+  // 2^31 slots at the most: a slot number, the special one included, is a u32
+  while (cap < 2 * n && cap < (1ull << 31)) cap <<= 1;
+  return cap;
+}
+
+constexpr int kSRows = 16;
+constexpr uint64_t kSTile = static_cast<uint64_t>(kSRows) * kThreads;
+constexpr int kSWaves = kThreads / 64;
+
+StaleWs stale_ws(uint64_t n, void* ws) {
+  StaleWs w;
+  w.cap = stale_cap(n);
+  const uint64_t blocks = (n + kSTile - 1) / kSTile;
+  uint8_t* p = static_cast<uint8_t*>(ws);
+  size_t o = 0;
+  auto take = [&](size_t bytes) {
+    uint8_t* q = p ? p + o : nullptr;
+    o += (bytes + 255) / 256 * 256;
+    return q;
+  };
+  w.table = reinterpret_cast<uint64_t*>(take(8 * w.cap));
+  w.hit = take(w.cap + 1);
+  w.bits = reinterpret_cast<uint32_t*>(take(w.cap));
+  w.slot_of = reinterpret_cast<uint32_t*>(take(4 * n));
+  w.cnt = reinterpret_cast<uint32_t*>(take(4 * (blocks + 1)));
+  w.tiles = reinterpret_cast<uint32_t*>(take(4 * (static_cast<size_t>(scan::tiles_for(blocks)) + 1)));
+  w.bytes = o;
+  return w;
+}
+
+uint32_t grid_for(uint64_t n, uint64_t per) {
+  const uint64_t g = (n + per - 1) / per;
+  return static_cast<uint32_t>(g == 0 ? 1 : (g < 2048 ? g : 2048));
+}
+
+// slot_of[i] = the slot thumbnail key[i] ends in: the first thread to claim an
+// empty slot (64-bit CAS) places the key, every other copy of it finds it.
+// Also sets the key's filter bit (one atomicOr per thumbnail).
+__global__ __launch_bounds__(kThreads) void k_stale_build(const uint64_t* __restrict__ key,
+                                                          uint64_t n, uint64_t* __restrict__ table,
+                                                          uint64_t cap,
+                                                          uint32_t* __restrict__ bits,
+                                                          uint32_t* __restrict__ slot_of) {
+  const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kThreads;
+  for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x; i < n;
+       i += stride) {
+    const uint64_t k = key[i];
+    uint64_t h = cap;
+    if (k != kEmptyKey) {
+      h = row_hash(k);
+      const uint64_t hb = h & (8 * cap - 1);
+      atomicOr(&bits[hb >> 5], 1u << (hb & 31));
+      h &= cap - 1;
+      for (;;) {
+        const unsigned long long prev =
+            atomicCAS(reinterpret_cast<unsigned long long*>(&table[h]),
+                      static_cast<unsigned long long>(kEmptyKey),
+                      static_cast<unsigned long long>(k));
+        if (prev == kEmptyKey || prev == k) break;
+        h = (h + 1) & (cap - 1);
+      }
+    }
+    slot_of[i] = static_cast<uint32_t>(h);
+  }
+}
+
+// One pass over a file_path column, one lane per row, kPRows rows per thread:
+// keys, has_key bytes and the rows' filter words are loaded unconditionally
+// (rows past the end read the last row) and masked afterwards, so a thread's
+// loads are in flight together (the RowBatch / k_mark idiom).  Only a row whose
+// filter bit is set reads the table, and only a probe that has to walk on
+// reads it again.  kHas = false: every row is keyed.
+//
+// The filter: bit (row_hash(key) & (8 cap - 1)) of `bits` is set for every
+// thumbnail key -- 16 bits or more per thumbnail, so 15 of 16 rows that own no
+// thumbnail stop at a word of a map of cap BYTES (2 MiB at 1 M thumbnails,
+// which an XCD's 4 MiB L2 holds) instead of pulling a line of the 8 x larger
+// table out of the Infinity Cache for 8 useful bytes.  Measured at 1 M
+// thumbnails, 30 % of the rows owning one: 100 M rows 2.58 -> 1.85 ms,
+// 12.5 M rows 0.53 -> 0.43 ms.
+constexpr int kPRows = 4;
+template <bool kHas>
+__global__ __launch_bounds__(kThreads) void k_stale_probe(const uint64_t* __restrict__ key,
+                                                          const uint8_t* __restrict__ has,
+                                                          uint64_t n,
+                                                          const uint64_t* __restrict__ table,
+                                                          uint64_t cap,
+                                                          const uint32_t* __restrict__ bits,
+                                                          uint8_t* __restrict__ hit) {
+  const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kThreads * kPRows;
+  for (uint64_t i0 = static_cast<uint64_t>(blockIdx.x) * kThreads * kPRows + threadIdx.x; i0 < n;
+       i0 += stride) {
+    uint64_t k[kPRows], h[kPRows], s[kPRows];
+    uint32_t w[kPRows];
+    uint8_t b[kPRows];
+    bool live[kPRows];
+#pragma unroll
+    for (int u = 0; u < kPRows; ++u)
+      k[u] = key[min(i0 + static_cast<uint64_t>(u) * kThreads, n - 1)];
+#pragma unroll
+    for (int u = 0; u < kPRows; ++u)
+      b[u] = kHas ? has[min(i0 + static_cast<uint64_t>(u) * kThreads, n - 1)] : uint8_t(1);
+#pragma unroll
+    for (int u = 0; u < kPRows; ++u) {
+      h[u] = row_hash(k[u]);
+      w[u] = bits[(h[u] & (8 * cap - 1)) >> 5];
+    }
+#pragma unroll
+    for (int u = 0; u < kPRows; ++u) {
+      live[u] = i0 + static_cast<uint64_t>(u) * kThreads < n && b[u] != 0;
+      if (live[u] && k[u] == kEmptyKey) hit[cap] = 1;
+      live[u] = live[u] && k[u] != kEmptyKey && (w[u] >> (h[u] & 31) & 1u);
+      h[u] &= cap - 1;
+    }
+#pragma unroll
+    for (int u = 0; u < kPRows; ++u) s[u] = live[u] ? table[h[u]] : kEmptyKey;
+#pragma unroll
+    for (int u = 0; u < kPRows; ++u) {
+      if (!live[u]) continue;
+      uint64_t hh = h[u], sk = s[u];
+      // load < 1 (<= 1/2 up to 2^30 thumbnails): an empty slot ends every walk
+      for (;;) {
+        if (sk == k[u]) {
+          hit[hh] = 1;
+          break;
+        }
+        if (sk == kEmptyKey) break;
+        hh = (hh + 1) & (cap - 1);
+        sk = table[hh];
+      }
+    }
+  }
+}
+
+// The thumbnail list in tiles of kSRows x kThreads positions: position
+// tile + k * kThreads + t, and (k, t) order is list order.  Bit k of the
+// result: this thread's k-th thumbnail is stale (its slot was not hit).
+__device__ __forceinline__ uint32_t stale_bits(const uint32_t* __restrict__ slot_of, uint64_t n,
+                                               uint64_t tile, const uint8_t* __restrict__ hit) {
+  uint32_t sl[kSRows];
+  uint8_t m[kSRows];
+#pragma unroll
+  for (int k = 0; k < kSRows; ++k) sl[k] = slot_of[min(tile + k * kThreads + threadIdx.x, n - 1)];
+#pragma unroll
+  for (int k = 0; k < kSRows; ++k) m[k] = hit[sl[k]];
+  uint32_t f = 0;
+#pragma unroll
+  for (int k = 0; k < kSRows; ++k)
+    f |= (tile + k * kThreads + threadIdx.x < n && m[k] == 0 ? 1u : 0u) << k;
+  return f;
+}
+
+__global__ __launch_bounds__(kThreads) void k_stale_count(const uint32_t* __restrict__ slot_of,
+                                                          uint64_t n,
+                                                          const uint8_t* __restrict__ hit,
+                                                          uint32_t* __restrict__ cnt) {
+  __shared__ uint32_t sw[kSWaves];
+  const uint64_t tile = static_cast<uint64_t>(blockIdx.x) * kSTile;
+  uint32_t c = __popc(stale_bits(slot_of, n, tile, hit));
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
+  if (__lane_id() == 0) sw[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t t = 0;
+    for (int w = 0; w < kSWaves; ++w) t += sw[w];
+    cnt[blockIdx.x] = t;
+  }
+}
+
+// stable compaction: tile b writes the positions of its stale thumbnails from
+// the scanned offset, in order
+__global__ __launch_bounds__(kThreads) void k_stale_write(const uint32_t* __restrict__ slot_of,
+                                                          uint64_t n,
+                                                          const uint8_t* __restrict__ hit,
+                                                          const uint32_t* __restrict__ offs,
+                                                          uint32_t* __restrict__ out) {
+  __shared__ uint32_t off[kSRows][kSWaves];
+  const uint64_t tile = static_cast<uint64_t>(blockIdx.x) * kSTile;
+  const uint32_t lane = __lane_id(), w = threadIdx.x >> 6;
+  const uint64_t lt = (1ull << lane) - 1ull;
+  const uint32_t f = stale_bits(slot_of, n, tile, hit);
+  uint32_t pre[kSRows];
+#pragma unroll
+  for (int k = 0; k < kSRows; ++k) {
+    const uint64_t b = __ballot(f >> k & 1u);
+    pre[k] = __popcll(b & lt);
+    if (lane == 0) off[k][w] = __popcll(b);
+  }
+  __syncthreads();
+  static_assert(kSRows * kSWaves == 64, "one wave scans the (row step, wave) counts");
+  if (threadIdx.x < 64) {  // (k, wave) order -- the array's order -- is list order
+    uint32_t* fl = &off[0][0];
+    const uint32_t a = fl[lane];
+    uint32_t inc = a;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t x = __shfl_up(inc, d);
+      if (lane >= static_cast<uint32_t>(d)) inc += x;
+    }
+    fl[lane] = offs[blockIdx.x] + inc - a;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < kSRows; ++k)
+    if (f >> k & 1u)
+      out[off[k][w] + pre[k]] = static_cast<uint32_t>(tile + k * kThreads + threadIdx.x);
+}
+
+// stale_start[d] = stale thumbnails before position dir_start[d]: the offset
+// of the boundary's tile plus the stale ones of that tile before the boundary
+// (at most a tile's rows, one wave per boundary).  A boundary past the list
+// (an inconsistent dir_start) counts as the list's end.
+__global__ __launch_bounds__(kThreads) void k_stale_dirs(const uint32_t* __restrict__ slot_of,
+                                                         uint64_t n,
+                                                         const uint8_t* __restrict__ hit,
+                                                         const uint32_t* __restrict__ offs,
+                                                         const uint32_t* __restrict__ dir_start,
+                                                         uint64_t n_bounds,
+                                                         uint32_t* __restrict__ stale_start) {
+  const uint32_t lane = __lane_id();
+  const uint64_t waves = static_cast<uint64_t>(gridDim.x) * kSWaves;
+  for (uint64_t d = static_cast<uint64_t>(blockIdx.x) * kSWaves + (threadIdx.x >> 6); d < n_bounds;
+       d += waves) {
+    const uint64_t p = min(static_cast<uint64_t>(dir_start[d]), n);
+    const uint64_t t = p / kSTile;
+    uint32_t c = 0;
+    for (uint64_t i = t * kSTile + lane; i < p; i += 64) c += hit[slot_of[i]] == 0 ? 1u : 0u;
+#pragma unroll
+    for (int x = 32; x > 0; x >>= 1) c += __shfl_xor(c, x);
+    if (lane == 0) stale_start[d] = offs[t] + c;
+  }
+}
+
+}  // namespace
+
+size_t stale_workspace_bytes(uint64_t n_thumbs) { return stale_ws(n_thumbs, nullptr).bytes; }
+
+hipError_t stale_build_launch(const uint64_t* thumb_key, uint64_t n, void* ws, hipStream_t s) {
+  const StaleWs w = stale_ws(n, ws);
+  // every call clears its own table: the workspace is shared and may hold anything
+  hipError_t e = hipMemsetAsync(w.table, 0xFF, 8 * w.cap, s);
+  if (e != hipSuccess) return e;
+  e = hipMemsetAsync(w.hit, 0, w.cap + 1, s);
+  if (e != hipSuccess) return e;
+  e = hipMemsetAsync(w.bits, 0, w.cap, s);
+  if (e != hipSuccess) return e;
+  if (n) k_stale_build<<<grid_for(n, kThreads), kThreads, 0, s>>>(thumb_key, n, w.table, w.cap,
+                                                                   w.bits, w.slot_of);
+  return hipGetLastError();
+}
+
+hipError_t stale_probe_launch(uint64_t n_thumbs, const uint64_t* col_key, const uint8_t* col_has,
+                              uint64_t rows, void* ws, hipStream_t s) {
+  if (rows == 0) return hipSuccess;
+  const StaleWs w = stale_ws(n_thumbs, ws);
+  const uint32_t grid = grid_for(rows, kThreads * kPRows);
+  if (col_has)
+    k_stale_probe<true><<<grid, kThreads, 0, s>>>(col_key, col_has, rows, w.table, w.cap, w.bits,
+                                                  w.hit);
+  else
+    k_stale_probe<false><<<grid, kThreads, 0, s>>>(col_key, nullptr, rows, w.table, w.cap, w.bits,
+                                                   w.hit);
+  return hipGetLastError();
+}
+
+hipError_t stale_compact_launch(uint64_t n, const uint32_t* dir_start, uint32_t n_dirs,
+                                uint32_t* stale, uint32_t* stale_start, void* ws, hipStream_t s) {
+  const StaleWs w = stale_ws(n, ws);
+  const uint64_t blocks = (n + kSTile - 1) / kSTile;
+  const uint64_t bounds = static_cast<uint64_t>(n_dirs) + 1;
+  if (blocks == 0) return hipMemsetAsync(stale_start, 0, 4 * bounds, s);
+  k_stale_count<<<static_cast<uint32_t>(blocks), kThreads, 0, s>>>(w.slot_of, n, w.hit, w.cnt);
+  scan::exclusive(w.cnt, blocks, w.cnt, w.tiles, nullptr, s);
+  k_stale_write<<<static_cast<uint32_t>(blocks), kThreads, 0, s>>>(w.slot_of, n, w.hit, w.cnt,
+                                                                   stale);
+  k_stale_dirs<<<grid_for(bounds, kSWaves), kThreads, 0, s>>>(w.slot_of, n, w.hit, w.cnt,
+                                                              dir_start, bounds, stale_start);
+  return hipGetLastError();
+}
+
+}  // namespace sdgpu
