@@ -221,8 +221,9 @@ int sdgpu_checksum_batch_device(sdgpu_ctx *ctx, const uint8_t *const *d_files,
                                 const uint64_t *lens, uint32_t n, uint8_t *d_out32, void *stream);
 /* Chaining value of one aligned subtree slice (for streaming hosts): len bytes
  * starting at chunk counter chunk_offset; chunk_offset must be a multiple of
- * the slice's chunk count rounded up to a power of two.  root=1 gives the digest
- * of a whole message (chunk_offset 0). */
+ * the slice's chunk count (ceil(len / 1024)) rounded up to a power of two, else
+ * -EINVAL; a slice of at most one chunk may sit at any counter.  root=1 gives
+ * the digest of a whole message (chunk_offset 0). */
 int sdgpu_subtree_device(sdgpu_ctx *ctx, const uint8_t *d_bytes, uint64_t len,
                          uint64_t chunk_offset, int root, uint8_t *d_out32, void *stream);
 /* Digest of a message from the chaining values of its consecutive aligned

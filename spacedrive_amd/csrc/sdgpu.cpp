@@ -1038,6 +1038,12 @@ int sdgpu_subtree_device(sdgpu_ctx* c, const uint8_t* d_bytes, uint64_t len, uin
                          int root, uint8_t* d_out32, void* stream) {
   if (!c || !d_bytes || !d_out32 || reinterpret_cast<uintptr_t>(d_bytes) % 16) return -EINVAL;
   if (root && chunk_offset != 0) return -EINVAL;
+  // a slice is a node of the message's tree only at a multiple of its chunk
+  // count rounded up to a power of two; a single chunk is a leaf anywhere
+  const uint64_t chunks = len / 1024 + (len % 1024 ? 1 : 0);
+  uint64_t span = 1;
+  while (span < chunks) span <<= 1;
+  if (chunk_offset & (span - 1)) return -EINVAL;
   std::lock_guard<std::mutex> g(c->mu);
   SD_TRY(hipSetDevice(c->device));
   hipStream_t s = pick(c, stream);

@@ -88,7 +88,9 @@ def checksum_batch_device(files, out=None, ctx=None, stream=None):
 
 
 def subtree_device(data, chunk_offset: int, root: bool, out=None, ctx=None, stream=None):
-    """Chaining value (root=False) or digest (root=True) of an aligned slice."""
+    """Chaining value (root=False) or digest (root=True) of an aligned slice:
+    chunk_offset a multiple of the slice's chunk count rounded up to a power
+    of two (any offset for a single chunk), else SdgpuError(EINVAL)."""
     import torch
     ctx = ctx or default_context(data.device.index)
     if out is None:

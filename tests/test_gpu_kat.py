@@ -13,7 +13,11 @@ then hashes all of them in one batched K1 call (cas_batch: digest bytes
 all 32 bytes).  Every GPU digest equals the recorded one, so a Balloon run
 driven by the GPU's digests would build the same messages and end on the
 same output -- and the last message's 32-byte GPU digest IS the reference's
-expected vector, compared with the bytes copied from hashing.rs."""
+expected vector, compared with the bytes copied from hashing.rs.
+
+These messages are single chunks; multi-chunk trees (parents, ROOT on a
+parent, chunk counters up to 2^64 - 2^32) are pinned to the BLAKE3 project's
+own implementation in tests/test_gpu_upstream_vectors.py."""
 import numpy as np
 import pytest
 
