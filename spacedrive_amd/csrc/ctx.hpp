@@ -4,7 +4,9 @@
 #pragma once
 
 #include <errno.h>
+#include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 #include <mutex>
@@ -222,6 +224,63 @@ inline hipStream_t pick(sdgpu_ctx* c, void* stream) {
   return s;
 }
 
+// SDGPU_POISON_WS=1 (tests only; read once): every buffer the library
+// allocates for itself starts as 0xA5 bytes, so a kernel that reads a word no
+// earlier kernel of the call wrote sees garbage rather than a fresh
+// allocation's zeros or the previous call's values (round 6: the class of the
+// SDGPU_SEG_GROUPS fault).  Buffers handed to the caller (sdgpu_alloc_device,
+// sdgpu_alloc_pinned) are not touched.
+inline bool poison_ws() {
+  static const bool on = std::getenv("SDGPU_POISON_WS") && std::getenv("SDGPU_POISON_WS")[0] == '1';
+  return on;
+}
+
+// Only under poison_ws(): fills a new device allocation and waits for the
+// fill, so no kernel of the call -- on whatever stream, blocking or not -- can
+// start before it has landed, and no later zero-fill of the library's own can
+// be overtaken by it.  One line per buffer on stderr lets a test prove that
+// its call really ran on poison.
+inline int poison_dev(void* p, size_t bytes, const char* what) {
+  fprintf(stderr, "sdgpu: poisoned %zu %s\n", bytes, what);
+  SD_TRY(hipMemset(p, 0xA5, bytes));
+  SD_TRY(hipDeviceSynchronize());
+  return 0;
+}
+
+inline void poison_host(void* p, size_t bytes, const char* what) {
+  fprintf(stderr, "sdgpu: poisoned %zu %s\n", bytes, what);
+  memset(p, 0xA5, bytes);
+}
+
+// The name a context's buffer is logged under (poison_ws() only).
+inline const char* buf_name(const sdgpu_ctx* c, const void* b) {
+#define SD_BUF_NAME(x) \
+  if (b == static_cast<const void*>(&c->x)) return #x
+  SD_BUF_NAME(batch_ws);
+  SD_BUF_NAME(tree_ws);
+  SD_BUF_NAME(dedup_ws);
+  SD_BUF_NAME(shard_ws);
+  SD_BUF_NAME(io_a);
+  SD_BUF_NAME(io_b);
+  SD_BUF_NAME(link_ws);
+  SD_BUF_NAME(stage_meta);
+  SD_BUF_NAME(small_ws);
+  SD_BUF_NAME(xs_send);
+  SD_BUF_NAME(xs_recv);
+  SD_BUF_NAME(xs_back);
+  SD_BUF_NAME(xs_ret);
+  SD_BUF_NAME(xs_rback);
+  SD_BUF_NAME(xs_cursor);
+  SD_BUF_NAME(xs_sink);
+  SD_BUF_NAME(xs_agree);
+#undef SD_BUF_NAME
+  for (int k = 0; k < 3; ++k)
+    if (b == static_cast<const void*>(&c->stage_slab[k])) return "stage_slab";
+  for (int k = 0; k < sdgpu_ctx::kPipeSlabs; ++k)
+    if (b == static_cast<const void*>(&c->pipe_d[k])) return "pipe_d";
+  return "buffer";
+}
+
 // Grow-only device buffer; frees the old one only after the context's work
 // has drained (a kernel may still read it).
 inline int ensure_dev(sdgpu_ctx* c, DevBuf& b, size_t bytes) {
@@ -236,12 +295,7 @@ inline int ensure_dev(sdgpu_ctx* c, DevBuf& b, size_t bytes) {
   const size_t want = align_up(std::max<size_t>(bytes, 1), size_t(1) << 20);
   SD_TRY(hipMalloc(&b.p, want));
   b.cap = want;
-  // SDGPU_POISON_WS=1 (tests only): a new workspace is filled with 0xA5
-  // bytes, so a kernel that reads a word no earlier kernel of the call wrote
-  // sees garbage rather than a fresh allocation's zeros or the previous
-  // call's values (round 6: the class of the SDGPU_SEG_GROUPS fault)
-  static const bool poison = std::getenv("SDGPU_POISON_WS") && std::getenv("SDGPU_POISON_WS")[0] == '1';
-  if (poison) SD_TRY(hipMemset(b.p, 0xA5, want));
+  if (poison_ws()) SD_TRY_RC(poison_dev(b.p, want, buf_name(c, &b)));
   return 0;
 }
 
@@ -262,17 +316,21 @@ inline int grow_dev_keep(sdgpu_ctx* c, DevBuf& b, size_t bytes, size_t keep) {
   void* np = nullptr;
   const size_t want = align_up(std::max<size_t>(bytes, 2 * b.cap), size_t(1) << 20);
   SD_TRY(hipMalloc(&np, want));
+  size_t kept = 0;
   if (b.p) {
     SD_TRY(hipStreamSynchronize(c->stream));
-    if (keep) SD_TRY(hipMemcpy(np, b.p, std::min(keep, b.cap), hipMemcpyDeviceToDevice));
+    kept = std::min(keep, b.cap);
+    if (kept) SD_TRY(hipMemcpy(np, b.p, kept, hipMemcpyDeviceToDevice));
     (void)hipFree(b.p);
   }
   b.p = np;
   b.cap = want;
+  if (poison_ws()) SD_TRY_RC(poison_dev(static_cast<uint8_t*>(np) + kept, want - kept, buf_name(c, &b)));
   return 0;
 }
 
-inline int ensure_pin(PinBuf& b, size_t bytes) {
+// Grow-only pinned buffer; `what` names it in the poison log.
+inline int ensure_pin(PinBuf& b, size_t bytes, const char* what) {
   if (bytes <= b.cap) return 0;
   if (b.p) (void)hipHostFree(b.p);
   b.p = nullptr;
@@ -280,6 +338,7 @@ inline int ensure_pin(PinBuf& b, size_t bytes) {
   const size_t want = align_up(std::max<size_t>(bytes, 1), size_t(1) << 16);
   SD_TRY(hipHostMalloc(&b.p, want, hipHostMallocDefault));
   b.cap = want;
+  if (poison_ws()) poison_host(b.p, want, what);
   return 0;
 }
 

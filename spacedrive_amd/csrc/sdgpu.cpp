@@ -87,7 +87,7 @@ int tree_launch(sdgpu_ctx* c, const TreeSeg* segs, uint32_t nseg, bool cv_input,
     SD_TRY(hipEventSynchronize(c->plan_evt));
     c->plan_pending = false;
   }
-  SD_TRY_RC(ensure_pin(c->plan_pin, tree_plan_bytes(nseg)));
+  SD_TRY_RC(ensure_pin(c->plan_pin, tree_plan_bytes(nseg), "plan_pin"));
   SD_TRY(tree_hash_launch(segs, nseg, cv_input, d_out, c->tree_ws.p, c->plan_pin.p, s, c->kt()));
   SD_TRY(hipEventRecord(c->plan_evt, s));
   c->plan_pending = true;
@@ -128,7 +128,7 @@ struct KindPass {
 // Pinned + device staging slot k of the context (grown on demand, kept).  Only
 // called when no work of the context is in flight.
 int pipe_slot(sdgpu_ctx* c, int k, size_t bytes) {
-  SD_TRY_RC(ensure_pin(c->pipe_h[k], bytes));
+  SD_TRY_RC(ensure_pin(c->pipe_h[k], bytes, "pipe_h"));
   SD_TRY_RC(ensure_dev(c, c->pipe_d[k], bytes));
   if (!c->pipe_evt[k]) SD_TRY(hipEventCreateWithFlags(&c->pipe_evt[k], hipEventDisableTiming));
   return 0;
@@ -400,8 +400,8 @@ int sdgpu_close(sdgpu_ctx* c) {
   if (c->last && c->last != c->stream) (void)hipStreamSynchronize(c->last);
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
   for (DevBuf* b : {&c->batch_ws, &c->tree_ws, &c->dedup_ws, &c->shard_ws, &c->io_a, &c->io_b,
-                    &c->link_ws, &c->stage_meta, &c->stage_slab[0], &c->stage_slab[1],
-                    &c->stage_slab[2]})
+                    &c->link_ws, &c->stage_meta, &c->small_ws, &c->stage_slab[0],
+                    &c->stage_slab[1], &c->stage_slab[2]})
     if (b->p) (void)hipFree(b->p);
   for (int k = 0; k < sdgpu_ctx::kPipeSlabs; ++k) {
     if (c->pipe_d[k].p) (void)hipFree(c->pipe_d[k].p);
@@ -1546,6 +1546,10 @@ int sdgpu_dedup(sdgpu_ctx* c, const uint64_t* key, const uint8_t* has_key, uint3
   const size_t o_key = 0, o_has = align_up(8ull * n, 256), o_rep = align_up(o_has + n, 256);
   const size_t total = align_up(o_rep + 4ull * n, 256);
   if (hipMalloc(&d, total) != hipSuccess) return -ENOMEM;
+  if (sdgpu::poison_ws() && sdgpu::poison_dev(d, total, "dedup_rows") != 0) {
+    (void)hipFree(d);
+    return -EIO;
+  }
   hipStream_t s = c->stream;
   do {
     if (hipMemcpyAsync(d + o_key, key, 8ull * n, hipMemcpyHostToDevice, s) != hipSuccess ||

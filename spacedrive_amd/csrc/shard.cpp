@@ -294,6 +294,7 @@ int index_alloc(sdgpu_ctx* c, DevBuf& b, uint64_t cap, IndexRef& r) {
   SD_TRY(hipMalloc(&p, bytes));
   b.p = p;
   b.cap = bytes;
+  if (sdgpu::poison_ws()) SD_TRY_RC(sdgpu::poison_dev(p, bytes, "index_table"));
   r.slots = static_cast<uint4*>(p);
   r.cap = cap;
   r.count = reinterpret_cast<unsigned long long*>(static_cast<uint8_t*>(p) + 16 * cap);
@@ -595,7 +596,7 @@ int exchange_forward(std::vector<RankJob>& J, int W, Clock::time_point t_start,
     const size_t o_summ = align_up(o_rpcnt + 8ull * W, 256);
     SD_TRY_RC(ensure_dev(j.c, j.c->xs_send, o_summ + 32));
     SD_TRY_RC(ensure_dev(j.c, j.c->shard_ws, shard_workspace_bytes(kShardBits)));
-    SD_TRY_RC(ensure_pin(j.c->xs_counts, 64ull * W));
+    SD_TRY_RC(ensure_pin(j.c->xs_counts, 64ull * W, "xs_counts"));
     uint8_t* b = static_cast<uint8_t*>(j.c->xs_send.p);
     j.srec = reinterpret_cast<uint32_t*>(b);
     j.spos = reinterpret_cast<uint32_t*>(b + o_pos);
@@ -737,7 +738,7 @@ int padded_epilogue(std::vector<RankJob>& J, int W, bool rep_form) {
   for (auto& j : J) {
     SD_TRY(hipSetDevice(j.c->device));
     sdgpu_comm* m = j.comm;
-    SD_TRY_RC(ensure_pin(m->summ, 64));
+    SD_TRY_RC(ensure_pin(m->summ, 64, "comm_summ"));
     if (!m->summ_evt) SD_TRY(hipEventCreateWithFlags(&m->summ_evt, hipEventDisableTiming));
     SD_TRY(hipMemcpyAsync(m->summ.p, j.summ, 32, hipMemcpyDeviceToHost, j.s));
     SD_TRY(hipEventRecord(m->summ_evt, j.s));
@@ -964,7 +965,7 @@ int agree_layout(std::vector<RankJob>& J, int W, uint64_t c1, int64_t code) {
   const Clock::time_point deadline = deadline_of(m->timeout_ms);
   SD_TRY(hipSetDevice(j.c->device));
   SD_TRY_RC(ensure_dev(j.c, j.c->xs_agree, 48ull * W));
-  SD_TRY_RC(ensure_pin(j.c->xs_counts, 64ull * W));
+  SD_TRY_RC(ensure_pin(j.c->xs_counts, 64ull * W, "xs_counts"));
   int64_t* h = static_cast<int64_t*>(j.c->xs_counts.p);
   int64_t* d = static_cast<int64_t*>(j.c->xs_agree.p);
   const int64_t mine[3] = {static_cast<int64_t>(c1), static_cast<int64_t>(m->agreed_n),
@@ -1633,6 +1634,10 @@ int sdgpu_dedup_batch(sdgpu_ctx* c, sdgpu_index* x, const uint64_t* key, const u
                o_rep = align_up(o_rank + 4ull * n, 256), total = align_up(o_rep + 4ull * n, 256);
   uint8_t* d = nullptr;
   if (hipMalloc(&d, total) != hipSuccess) return -ENOMEM;
+  if (sdgpu::poison_ws() && sdgpu::poison_dev(d, total, "dedup_batch_rows") != 0) {
+    (void)hipFree(d);
+    return -EIO;
+  }
   std::vector<uint32_t> rank(n);
   for (uint32_t i = 0; i < n; ++i) rank[i] = first_rank + i;
   hipStream_t s = c->stream;
@@ -1829,6 +1834,7 @@ int sdgpu_dedup_sharded(sdgpu_ctx* const* ctx, int ngpu, const uint64_t* key,
       rc = -ENOMEM;
       break;
     }
+    if (sdgpu::poison_ws() && (rc = sdgpu::poison_dev(buf[r], tot, "dedup_sharded_rows"))) break;
     std::vector<uint32_t> rk(cnt[r]);
     for (uint64_t i = 0; i < cnt[r]; ++i) rk[i] = static_cast<uint32_t>(first[r] + i);
     dk[r] = reinterpret_cast<const uint64_t*>(buf[r]);

@@ -4,7 +4,7 @@ Round 6: the SDGPU_SEG_GROUPS fault was a group kernel
 reading a bucket end that nothing had written yet -- harmless on a warm
 workspace (the previous call's value), fatal on a fresh one.  With
 SDGPU_POISON_WS=1 every workspace the library allocates starts as 0xA5
-bytes (csrc/ctx.hpp ensure_dev), so such a read yields garbage instead of a
+bytes (csrc/ctx.hpp poison_dev), so such a read yields garbage instead of a
 lucky zero or a stale-but-right value.  A fresh child process (the knob is
 read once) runs the grouping paths on their FIRST calls -- the one-level
 12-bit and the two-level partitions, the fused write set, the rep API, the
@@ -31,7 +31,6 @@ from oracle import oracle as O
 from spacedrive_amd import dedup
 from spacedrive_amd._native import Context
 
-ctx = Context(0)
 out = {}
 
 
@@ -39,24 +38,32 @@ def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
+# Poison is there only on the call that allocates a workspace, and the forms
+# share the grow-only workspaces of a context: a context of its own per form
+# and per size, so that every one of these calls is a first call.
 for n in (4_000_000, 13_000_000):  # one-level 12-bit, two-level
     k, h, rk = O.synth_dedup_rows(300 + n % 7, n, int(n * 0.8), 0, n)
     ref = O.group_reps(k, h, 100)
     rc, rlr, rlo = O.link_batch(ref, None, None, 0)
     dk, dh = dev(k.view(np.int64)), dev(h)
     # fused grouping + write set (implicit ranks), first call of this size
+    ctx = Context(0)
     who, obj, cnt = dedup.group_link_device(dk, dh, None, None, 0, 100, ctx=ctx, trim=False)
     torch.cuda.synchronize()
     c, l, e = (int(x) for x in cnt.cpu().tolist())
     fc, flr, flo = dedup.split_link_lists(who[:e].cpu().numpy(), obj[:e].cpu().numpy())
     out[f"fused_{n}"] = int(not (np.array_equal(fc, rc) and np.array_equal(flr, rlr)
                                  and np.array_equal(flo, rlo)))
+    ctx.close()
     # the rep API with explicit ranks (16-byte records)
+    ctx = Context(0)
     dr = dev(rk.view(np.int32))
     rep = dedup.HipOps(ctx).group_rows(dk, dh, dr, 100, 0)
     torch.cuda.synchronize()
     out[f"rep_{n}"] = int(np.count_nonzero(rep.cpu().numpy().view(np.uint32) != ref))
+    ctx.close()
 # Object index + padded exchange through a one-rank communicator (fresh buffers)
+ctx = Context(0)
 n = 2_000_000
 k, h, rk = O.synth_dedup_rows(77, n, 1_600_000, 0, n)
 ref = O.group_reps(k, h, 100)
