@@ -7,6 +7,8 @@
 //!   -- core/src/object/file_identifier/mod.rs:100-336 (`identifier.rs` here)
 //! * the stale-thumbnail sweep `process_clean_up`
 //!   -- core/src/object/thumbnail_remover.rs:236-367 (`thumbnail_remover.rs` here)
+//! * the thumbnailer's work list, the stat per row of `thumbnail::process`
+//!   -- core/src/object/media/thumbnail/mod.rs:204-359 (`thumbnailer.rs` here)
 //!
 //! Blocking library calls run inside `spawn_blocking`, as the reference's
 //! `tokio::fs` calls do, so the async runtime never blocks.  Errors are the
@@ -22,6 +24,7 @@ pub mod hash;
 pub mod identifier;
 pub mod job;
 pub mod thumbnail_remover;
+pub mod thumbnailer;
 
 use std::{
     ffi::{CStr, CString},

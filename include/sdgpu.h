@@ -725,6 +725,57 @@ int sdgpu_stale_thumbnails(sdgpu_ctx *ctx, const uint64_t *thumb_key, uint64_t n
                            const uint64_t *const *col_key, const uint8_t *const *col_has_key,
                            const uint64_t *col_rows, uint32_t n_cols, uint32_t *stale,
                            uint32_t *stale_start);
+/* (ABI 6, additive) Thumbnailer work list (core/src/object/media/thumbnail/
+ * mod.rs:204-359, process): which file_paths still need a thumbnail.  The
+ * reference builds <base>/<cas_id[0..2]>/<cas_id>.webp for every row of a step
+ * (:254-256), stats it (:273), skips the row when the file exists and
+ * `regenerate` is off (:301-307) and generates otherwise (:327-343), in steps
+ * of 10 rows (media_processor/job.rs:34,151; shallow.rs:31,105) of one query
+ * (media_processor/mod.rs:74-116); the explorer stats the same path per item
+ * (api/search.rs:540-547, :686-695; library/library.rs:122-130
+ * thumbnail_exists).  Here: d_thumb_key[n_thumbs] = the cas keys of the
+ * thumbnails on disk (duplicates allowed); one column of file_path rows in
+ * ascending id order, d_key[n], d_has_key[n] (NULL = every row keyed),
+ * d_eligible[n] (NULL = every row eligible; the caller's WHERE clause:
+ * location, extension list, sub-path).  flags: 0 or SDGPU_THUMBS_REGENERATE.
+ *   present[i] = 1 iff has_key[i] != 0 and key[i] is a thumbnail key (whatever
+ *     eligible[i] is: thumbnail_exists of the row's cas_id), else 0;
+ *   row i is a candidate iff has_key[i] != 0, eligible[i] != 0 and
+ *     (present[i] == 0 or REGENERATE);
+ *   row i is a work row iff it is a candidate and no candidate j < i has
+ *     key[j] == key[i]; rows that are no candidates shadow nothing.
+ * d_work[0 .. W) = the work rows ordered by shard directory (key & 0xFF, the
+ * first cas byte, shard.rs:4-8), ascending inside a directory; nothing is
+ * written past W (capacity n).  d_dir_start[0..256] = exclusive offsets into
+ * d_work, d_dir_start[256] = W.  d_stats[4] = keyed rows with present == 1;
+ * keyed and eligible rows; those of them with present == 1; W.  d_present
+ * [n] may be NULL.  The keys 0 and ~0 are ordinary keys on both sides.
+ * Presence only (the explorer's call): d_work and d_dir_start both NULL --
+ * d_present and d_stats[0] alone, no grouping runs, d_stats[1..3] = 0.
+ * n == 0: zeros in d_dir_start and d_stats; n_thumbs == 0: nothing is present.
+ * Deviation: the reference generates two rows of one step that share a cas_id
+ * twice (the same file written twice) and counts both as created; here every
+ * distinct cas_id is a work row once, the files on disk afterwards are the same
+ * set, and created / skipped differ by exactly the number of in-step copies.
+ * -EINVAL: d_present and d_work both NULL, exactly one of d_work / d_dir_start
+ * NULL, NULL d_stats, NULL d_key with n > 0, NULL d_thumb_key with n_thumbs >
+ * 0, any other flag bit, n >= 2^31 or n_thumbs >= 2^31.  Asynchronous on
+ * `stream`, no synchronisation. */
+#define SDGPU_THUMBS_REGENERATE 1u
+int sdgpu_thumbnail_worklist_device(sdgpu_ctx *ctx, const uint64_t *d_thumb_key,
+                                    uint64_t n_thumbs, const uint64_t *d_key,
+                                    const uint8_t *d_has_key, const uint8_t *d_eligible,
+                                    uint64_t n, uint32_t flags, uint8_t *d_present,
+                                    uint32_t *d_work, uint32_t *d_dir_start, uint32_t *d_stats,
+                                    void *stream);
+/* (ABI 6, additive) The same on host arrays (what the media processor calls
+ * with the rows it fetched): copy in, run, copy out; returns when done.  Only
+ * dir_start[256] entries of work travel back. */
+int sdgpu_thumbnail_worklist(sdgpu_ctx *ctx, const uint64_t *thumb_key, uint64_t n_thumbs,
+                             const uint64_t *key, const uint8_t *has_key,
+                             const uint8_t *eligible, uint64_t n, uint32_t flags,
+                             uint8_t *present, uint32_t *work, uint32_t *dir_start,
+                             uint32_t *stats);
 
 /* ---- synthetic corpora (bench / tests; same content function as oracle/) ---- */
 int sdgpu_synth_cas_arena_device(sdgpu_ctx *ctx, const uint64_t *d_sizes, const uint64_t *d_seeds,

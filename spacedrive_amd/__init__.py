@@ -6,12 +6,14 @@ Drop-in for sd-core's hot path:
   file_identifier.*              core/src/object/file_identifier/mod.rs
   dedup.*                        identifier_job_step's Object grouping
   thumbnail_remover.*            core/src/object/thumbnail_remover.rs:236-367
+  thumbnailer.*                  core/src/object/media/thumbnail/mod.rs:204-359
 All compute runs in libsdgpu.so (HIP kernels for gfx950); there is no CPU path.
 """
 from ._native import Context, SdgpuError, default_context, load  # noqa: F401
 from .cas import generate_cas_id  # noqa: F401
 from .validation import file_checksum  # noqa: F401
 from . import thumbnail_remover  # noqa: F401
+from . import thumbnailer  # noqa: F401
 from .thumbnail_remover import ThumbnailRemover, process_clean_up  # noqa: F401
 
 __version__ = "0.1.0"

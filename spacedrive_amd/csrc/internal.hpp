@@ -372,6 +372,27 @@ hipError_t stale_probe_launch(uint64_t n_thumbs, const uint64_t* col_key, const 
                               uint64_t rows, void* ws, hipStream_t s);
 hipError_t stale_compact_launch(uint64_t n_thumbs, const uint32_t* dir_start, uint32_t n_dirs,
                                 uint32_t* stale, uint32_t* stale_start, void* ws, hipStream_t s);
+// The probe in the other direction, after stale_build_launch in the same ws:
+// present[i] / cand[i] for every row (k_thumb_present); cand null: present and
+// stats[0] only.  stats[0..2] must be zero on entry.
+hipError_t thumb_present_launch(uint64_t n_thumbs, const uint64_t* key, const uint8_t* has,
+                                const uint8_t* elig, uint64_t rows, bool regen, uint8_t* present,
+                                uint8_t* cand, uint32_t* stats, void* ws, hipStream_t s,
+                                KTimer* timer = nullptr);
+
+// ---- thumbnailer work list (thumbnailer.hip) ---------------------------------------
+// The missing-thumbnail semi-join of include/sdgpu.h (sdgpu_thumbnail_worklist_
+// device): table of the thumbnail keys, presence probe, first-of-key over the
+// candidates (dedup_local_launch in group_ws = dedup_workspace_bytes(n) bytes of
+// its own), work mask, shard order, offsets.  ws: thumb_worklist_workspace_bytes
+// bytes, of which the call initialises all it reads.  work / dir_start both
+// null: presence only (no group_ws needed); present null: kept in ws.
+size_t thumb_worklist_workspace_bytes(uint64_t n_thumbs, uint64_t n, bool with_work);
+hipError_t thumb_worklist_launch(const uint64_t* thumb_key, uint64_t n_thumbs, const uint64_t* key,
+                                 const uint8_t* has, const uint8_t* elig, uint64_t n, bool regen,
+                                 uint8_t* present, uint32_t* work, uint32_t* dir_start,
+                                 uint32_t* stats, void* ws, void* group_ws, hipStream_t s,
+                                 KTimer* timer = nullptr);
 
 // ---- Object link batch (K7) ----------------------------------------------------
 size_t link_workspace_bytes(uint64_t n);

@@ -1722,6 +1722,97 @@ int sdgpu_stale_thumbnails(sdgpu_ctx* c, const uint64_t* thumb_key, uint64_t n_t
   return 0;
 }
 
+// Thumbnailer work list (thumbnailer.hip).  The checks both variants share.
+static bool worklist_args_ok(sdgpu_ctx* c, const uint64_t* thumb_key, uint64_t n_thumbs,
+                             const uint64_t* key, uint64_t n, uint32_t flags,
+                             const uint8_t* present, const uint32_t* work,
+                             const uint32_t* dir_start, const uint32_t* stats) {
+  if (!c || !stats || (flags & ~SDGPU_THUMBS_REGENERATE)) return false;
+  if ((work == nullptr) != (dir_start == nullptr) || (!work && !present)) return false;
+  if (n >= (1ull << 31) || n_thumbs >= (1ull << 31)) return false;
+  return !(n && !key) && !(n_thumbs && !thumb_key);
+}
+
+// The launch sequence on device arrays, the table and the call's scratch at
+// `ws`; the caller holds the context's lock.
+static int worklist_run(sdgpu_ctx* c, const uint64_t* d_thumb_key, uint64_t n_thumbs,
+                        const uint64_t* d_key, const uint8_t* d_has_key,
+                        const uint8_t* d_eligible, uint64_t n, uint32_t flags, uint8_t* d_present,
+                        uint32_t* d_work, uint32_t* d_dir_start, uint32_t* d_stats, void* ws,
+                        hipStream_t s) {
+  if (d_work && n) SD_TRY_RC(ensure_dev(c, c->dedup_ws, dedup_workspace_bytes(n)));
+  SD_TRY(thumb_worklist_launch(d_thumb_key, n_thumbs, d_key, d_has_key, d_eligible, n,
+                               (flags & SDGPU_THUMBS_REGENERATE) != 0, d_present, d_work,
+                               d_dir_start, d_stats, ws, c->dedup_ws.p, s, c->kt()));
+  return 0;
+}
+
+int sdgpu_thumbnail_worklist_device(sdgpu_ctx* c, const uint64_t* d_thumb_key, uint64_t n_thumbs,
+                                    const uint64_t* d_key, const uint8_t* d_has_key,
+                                    const uint8_t* d_eligible, uint64_t n, uint32_t flags,
+                                    uint8_t* d_present, uint32_t* d_work, uint32_t* d_dir_start,
+                                    uint32_t* d_stats, void* stream) {
+  if (!worklist_args_ok(c, d_thumb_key, n_thumbs, d_key, n, flags, d_present, d_work, d_dir_start,
+                        d_stats))
+    return -EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  SD_TRY(hipSetDevice(c->device));
+  hipStream_t s = pick(c, stream);
+  SD_TRY_RC(ensure_dev(c, c->link_ws,
+                       thumb_worklist_workspace_bytes(n_thumbs, n, d_work != nullptr)));
+  return worklist_run(c, d_thumb_key, n_thumbs, d_key, d_has_key, d_eligible, n, flags, d_present,
+                      d_work, d_dir_start, d_stats, c->link_ws.p, s);
+}
+
+int sdgpu_thumbnail_worklist(sdgpu_ctx* c, const uint64_t* thumb_key, uint64_t n_thumbs,
+                             const uint64_t* key, const uint8_t* has_key, const uint8_t* eligible,
+                             uint64_t n, uint32_t flags, uint8_t* present, uint32_t* work,
+                             uint32_t* dir_start, uint32_t* stats) {
+  if (!worklist_args_ok(c, thumb_key, n_thumbs, key, n, flags, present, work, dir_start, stats))
+    return -EINVAL;
+  if (n == 0) {
+    if (dir_start) memset(dir_start, 0, 4 * 257);
+    memset(stats, 0, 4 * 4);
+    return 0;
+  }
+  std::lock_guard<std::mutex> g(c->mu);
+  SD_TRY(hipSetDevice(c->device));
+  hipStream_t s = pick(c, nullptr);
+  // workspace | thumbnail keys | keys | has_key | eligible | present | work |
+  // dir_start, stats in the context's link workspace
+  const size_t o_tk = align_up(thumb_worklist_workspace_bytes(n_thumbs, n, work != nullptr), 256);
+  const size_t o_key = o_tk + align_up(8 * n_thumbs, 256);
+  const size_t o_has = o_key + align_up(8 * n, 256);
+  const size_t o_el = o_has + align_up(has_key ? n : 0, 256);
+  const size_t o_pr = o_el + align_up(eligible ? n : 0, 256);
+  const size_t o_work = o_pr + align_up(present ? n : 0, 256);
+  const size_t o_dir = o_work + align_up(work ? 4 * n : 0, 256);
+  SD_TRY_RC(ensure_dev(c, c->link_ws, o_dir + 4 * (257 + 4)));
+  uint8_t* base = static_cast<uint8_t*>(c->link_ws.p);
+  uint64_t* dtk = reinterpret_cast<uint64_t*>(base + o_tk);
+  uint64_t* dk = reinterpret_cast<uint64_t*>(base + o_key);
+  uint8_t* dpr = present ? base + o_pr : nullptr;
+  uint32_t* dwork = work ? reinterpret_cast<uint32_t*>(base + o_work) : nullptr;
+  uint32_t* ddir = reinterpret_cast<uint32_t*>(base + o_dir);
+  uint32_t* dstats = ddir + 257;
+  if (n_thumbs) SD_TRY(hipMemcpyAsync(dtk, thumb_key, 8 * n_thumbs, hipMemcpyHostToDevice, s));
+  SD_TRY(hipMemcpyAsync(dk, key, 8 * n, hipMemcpyHostToDevice, s));
+  if (has_key) SD_TRY(hipMemcpyAsync(base + o_has, has_key, n, hipMemcpyHostToDevice, s));
+  if (eligible) SD_TRY(hipMemcpyAsync(base + o_el, eligible, n, hipMemcpyHostToDevice, s));
+  SD_TRY_RC(worklist_run(c, dtk, n_thumbs, dk, has_key ? base + o_has : nullptr,
+                         eligible ? base + o_el : nullptr, n, flags, dpr, dwork,
+                         work ? ddir : nullptr, dstats, base, s));
+  SD_TRY(hipMemcpyAsync(stats, dstats, 4 * 4, hipMemcpyDeviceToHost, s));
+  if (work) SD_TRY(hipMemcpyAsync(dir_start, ddir, 4 * 257, hipMemcpyDeviceToHost, s));
+  if (present) SD_TRY(hipMemcpyAsync(present, dpr, n, hipMemcpyDeviceToHost, s));
+  SD_TRY(hipStreamSynchronize(s));
+  // only the work rows travel back
+  if (work && dir_start[256])
+    SD_TRY(hipMemcpy(work, dwork, 4 * static_cast<size_t>(dir_start[256]),
+                     hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int sdgpu_synth_vary_keys_device(sdgpu_ctx* c, uint64_t* d_key, const uint8_t* d_vary,
                                  uint64_t n, uint64_t step, void* stream) {
   if (!c || (n && (!d_key || !d_vary))) return -EINVAL;

@@ -24,6 +24,9 @@
 // boundary gets its offset into that list from its tile's offset plus a count
 // of the tile's rows before it.  A key listed twice (a misplaced copy in a
 // second directory) ends in one slot, so both copies get one answer.
+//
+// The same table answers the opposite question, which file_paths still need a
+// thumbnail (thumbnailer.hip): k_thumb_present probes it per row.
 #include "internal.hpp"
 #include "rows_device.hpp"
 #include "scan_device.hpp"
@@ -39,7 +42,7 @@ constexpr uint64_t kMinCap = 1024;
 struct StaleWs {
   uint64_t cap;       // slots; the key ~0 owns slot `cap`
   uint64_t* table;    // [cap]
-  uint8_t* hit;       // [cap + 1]
+  uint8_t* hit;       // [cap + 2]; hit[cap + 1]: a thumbnail key is ~0 (set by the build)
   uint32_t* bits;     // [cap / 4] the probe's filter: a bit per thumbnail key's hash
   uint32_t* slot_of;  // [n]
   uint32_t* cnt;      // [blocks + 1] stale per tile, then their offsets
@@ -70,7 +73,7 @@ StaleWs stale_ws(uint64_t n, void* ws) {
     return q;
   };
   w.table = reinterpret_cast<uint64_t*>(take(8 * w.cap));
-  w.hit = take(w.cap + 1);
+  w.hit = take(w.cap + 2);
   w.bits = reinterpret_cast<uint32_t*>(take(w.cap));
   w.slot_of = reinterpret_cast<uint32_t*>(take(4 * n));
   w.cnt = reinterpret_cast<uint32_t*>(take(4 * (blocks + 1)));
@@ -86,12 +89,15 @@ uint32_t grid_for(uint64_t n, uint64_t per) {
 
 // slot_of[i] = the slot thumbnail key[i] ends in: the first thread to claim an
 // empty slot (64-bit CAS) places the key, every other copy of it finds it.
-// Also sets the key's filter bit (one atomicOr per thumbnail).
+// Also sets the key's filter bit (one atomicOr per thumbnail), and for the key
+// ~0, which has no slot in the table, the byte hit[cap + 1] that tells
+// k_thumb_present the thumbnail exists (a plain byte store, idempotent).
 __global__ __launch_bounds__(kThreads) void k_stale_build(const uint64_t* __restrict__ key,
                                                           uint64_t n, uint64_t* __restrict__ table,
                                                           uint64_t cap,
                                                           uint32_t* __restrict__ bits,
-                                                          uint32_t* __restrict__ slot_of) {
+                                                          uint32_t* __restrict__ slot_of,
+                                                          uint8_t* __restrict__ hit) {
   const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kThreads;
   for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kThreads + threadIdx.x; i < n;
        i += stride) {
@@ -110,6 +116,8 @@ __global__ __launch_bounds__(kThreads) void k_stale_build(const uint64_t* __rest
         if (prev == kEmptyKey || prev == k) break;
         h = (h + 1) & (cap - 1);
       }
+    } else {
+      hit[cap + 1] = 1;
     }
     slot_of[i] = static_cast<uint32_t>(h);
   }
@@ -180,6 +188,104 @@ __global__ __launch_bounds__(kThreads) void k_stale_probe(const uint64_t* __rest
         sk = table[hh];
       }
     }
+  }
+}
+
+// The probe in the other direction (the thumbnailer's work list,
+// thumbnailer.hip): a per-row answer instead of hit[slot].  Same loads, filter
+// bit first, same walk; a block's threads share their trip count, so every
+// ballot is of whole waves.  Per row two plain coalesced byte stores:
+//   present[i] = keyed and the key is among the thumbnail keys (the key ~0:
+//                hit[cap + 1], which the build set);
+//   cand[i]    = keyed, eligible, and (not present or regen)  (cand non-null).
+// stats (zeroed by the caller) += [0] present rows, and with cand [1] keyed
+// eligible rows, [2] those of them that are present: wave ballots, summed per
+// block, one atomic per block and counter.  kHas / kElig = false: every row is
+// keyed / eligible.
+template <bool kHas, bool kElig>
+__global__ __launch_bounds__(kThreads) void k_thumb_present(const uint64_t* __restrict__ key,
+                                                            const uint8_t* __restrict__ has,
+                                                            const uint8_t* __restrict__ elig,
+                                                            uint64_t n,
+                                                            const uint64_t* __restrict__ table,
+                                                            uint64_t cap,
+                                                            const uint32_t* __restrict__ bits,
+                                                            const uint8_t* __restrict__ hit,
+                                                            bool regen,
+                                                            uint8_t* __restrict__ present,
+                                                            uint8_t* __restrict__ cand,
+                                                            uint32_t* __restrict__ stats) {
+  __shared__ uint32_t sw[kThreads / 64][3];
+  const bool special = hit[cap + 1] != 0;
+  const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kThreads * kPRows;
+  uint32_t c0 = 0, c1 = 0, c2 = 0;  // wave-uniform
+  for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * kThreads * kPRows; base < n;
+       base += stride) {
+    const uint64_t i0 = base + threadIdx.x;
+    uint64_t k[kPRows], h[kPRows], s[kPRows];
+    uint32_t w[kPRows];
+    uint8_t b[kPRows], e[kPRows];
+    bool in[kPRows], keyed[kPRows], live[kPRows];
+#pragma unroll
+    for (int u = 0; u < kPRows; ++u)
+      k[u] = key[min(i0 + static_cast<uint64_t>(u) * kThreads, n - 1)];
+#pragma unroll
+    for (int u = 0; u < kPRows; ++u)
+      b[u] = kHas ? has[min(i0 + static_cast<uint64_t>(u) * kThreads, n - 1)] : uint8_t(1);
+#pragma unroll
+    for (int u = 0; u < kPRows; ++u)
+      e[u] = kElig ? elig[min(i0 + static_cast<uint64_t>(u) * kThreads, n - 1)] : uint8_t(1);
+#pragma unroll
+    for (int u = 0; u < kPRows; ++u) {
+      h[u] = row_hash(k[u]);
+      w[u] = bits[(h[u] & (8 * cap - 1)) >> 5];
+    }
+#pragma unroll
+    for (int u = 0; u < kPRows; ++u) {
+      in[u] = i0 + static_cast<uint64_t>(u) * kThreads < n;
+      keyed[u] = in[u] && b[u] != 0;
+      live[u] = keyed[u] && k[u] != kEmptyKey && (w[u] >> (h[u] & 31) & 1u);
+      h[u] &= cap - 1;
+    }
+#pragma unroll
+    for (int u = 0; u < kPRows; ++u) s[u] = live[u] ? table[h[u]] : kEmptyKey;
+#pragma unroll
+    for (int u = 0; u < kPRows; ++u) {
+      bool p = keyed[u] && k[u] == kEmptyKey && special;
+      if (live[u]) {
+        uint64_t hh = h[u], sk = s[u];
+        // load < 1 (<= 1/2 up to 2^30 thumbnails): an empty slot ends every walk
+        for (;;) {
+          if (sk == k[u]) {
+            p = true;
+            break;
+          }
+          if (sk == kEmptyKey) break;
+          hh = (hh + 1) & (cap - 1);
+          sk = table[hh];
+        }
+      }
+      const bool q = keyed[u] && e[u] != 0;
+      if (in[u]) {
+        const uint64_t i = i0 + static_cast<uint64_t>(u) * kThreads;
+        present[i] = p ? 1 : 0;
+        if (cand) cand[i] = q && (!p || regen) ? 1 : 0;
+      }
+      c0 += __popcll(__ballot(p));
+      c1 += __popcll(__ballot(q));
+      c2 += __popcll(__ballot(q && p));
+    }
+  }
+  if (__lane_id() == 0) {
+    sw[threadIdx.x >> 6][0] = c0;
+    sw[threadIdx.x >> 6][1] = c1;
+    sw[threadIdx.x >> 6][2] = c2;
+  }
+  __syncthreads();
+  if (threadIdx.x < (cand ? 3u : 1u)) {
+    uint32_t t = 0;
+    for (int v = 0; v < kThreads / 64; ++v) t += sw[v][threadIdx.x];
+    if (t) atomicAdd(&stats[threadIdx.x], t);
   }
 }
 
@@ -292,12 +398,12 @@ hipError_t stale_build_launch(const uint64_t* thumb_key, uint64_t n, void* ws, h
   // every call clears its own table: the workspace is shared and may hold anything
   hipError_t e = hipMemsetAsync(w.table, 0xFF, 8 * w.cap, s);
   if (e != hipSuccess) return e;
-  e = hipMemsetAsync(w.hit, 0, w.cap + 1, s);
+  e = hipMemsetAsync(w.hit, 0, w.cap + 2, s);
   if (e != hipSuccess) return e;
   e = hipMemsetAsync(w.bits, 0, w.cap, s);
   if (e != hipSuccess) return e;
   if (n) k_stale_build<<<grid_for(n, kThreads), kThreads, 0, s>>>(thumb_key, n, w.table, w.cap,
-                                                                   w.bits, w.slot_of);
+                                                                   w.bits, w.slot_of, w.hit);
   return hipGetLastError();
 }
 
@@ -312,6 +418,25 @@ hipError_t stale_probe_launch(uint64_t n_thumbs, const uint64_t* col_key, const 
   else
     k_stale_probe<false><<<grid, kThreads, 0, s>>>(col_key, nullptr, rows, w.table, w.cap, w.bits,
                                                    w.hit);
+  return hipGetLastError();
+}
+
+hipError_t thumb_present_launch(uint64_t n_thumbs, const uint64_t* key, const uint8_t* has,
+                                const uint8_t* elig, uint64_t rows, bool regen, uint8_t* present,
+                                uint8_t* cand, uint32_t* stats, void* ws, hipStream_t s,
+                                KTimer* timer) {
+  if (rows == 0) return hipSuccess;
+  const StaleWs w = stale_ws(n_thumbs, ws);
+  const uint32_t grid = grid_for(rows, kThreads * kPRows);
+  KScope k(timer, "thumb_present", s);
+#define SD_THUMB_PRESENT(H, E)                                                                   \
+  k_thumb_present<H, E><<<grid, kThreads, 0, s>>>(key, has, elig, rows, w.table, w.cap, w.bits, \
+                                                  w.hit, regen, present, cand, stats)
+  if (has && elig) SD_THUMB_PRESENT(true, true);
+  else if (has) SD_THUMB_PRESENT(true, false);
+  else if (elig) SD_THUMB_PRESENT(false, true);
+  else SD_THUMB_PRESENT(false, false);
+#undef SD_THUMB_PRESENT
   return hipGetLastError();
 }
 
