@@ -9,6 +9,8 @@
 //!   -- core/src/object/thumbnail_remover.rs:236-367 (`thumbnail_remover.rs` here)
 //! * the thumbnailer's work list, the stat per row of `thumbnail::process`
 //!   -- core/src/object/media/thumbnail/mod.rs:204-359 (`thumbnailer.rs` here)
+//! * the indexer's rescan diff (to_create / to_update / to_remove)
+//!   -- core/src/location/indexer/walk.rs:309-381,624-636 (`indexer.rs` here)
 //!
 //! Blocking library calls run inside `spawn_blocking`, as the reference's
 //! `tokio::fs` calls do, so the async runtime never blocks.  Errors are the
@@ -22,6 +24,7 @@ pub mod burst;
 pub mod cas;
 pub mod hash;
 pub mod identifier;
+pub mod indexer;
 pub mod job;
 pub mod thumbnail_remover;
 pub mod thumbnailer;

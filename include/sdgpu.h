@@ -776,6 +776,83 @@ int sdgpu_thumbnail_worklist(sdgpu_ctx *ctx, const uint64_t *thumb_key, uint64_t
                              const uint8_t *eligible, uint64_t n, uint32_t flags,
                              uint8_t *present, uint32_t *work, uint32_t *dir_start,
                              uint32_t *stats);
+/* (ABI 6, additive) Indexer rescan diff (core/src/location/indexer/walk.rs:
+ * 309-381 filter_existing_paths, :624-636 the per-directory to_remove query;
+ * indexer/mod.rs:305-331 file_paths_db_fetcher_fn, :338-388
+ * to_remove_db_fetcher_fn): which walked entries are new (to_create), which
+ * changed behind the library's back (to_update; the indexer then clears their
+ * cas_id and Object, indexer/mod.rs:207-215) and which file_path rows are gone
+ * from disk (to_remove), for ONE location in one call.  Walking, the indexer
+ * rules and the database writes stay with the caller.
+ * A 64-bit key stands for a row's unique tuple (materialized_path, name,
+ * extension), a second one for a directory's materialized_path_for_children()
+ * (file_path_helper/isolated_file_path_data.rs:150-158); only equality of keys
+ * is used, and the caller makes the answer exact by comparing the strings of
+ * every matched pair.
+ *   Walked entries (walk.rs's indexed_paths: accepted by the rules, ancestors
+ *   included): d_w_key[n_w]; d_w_flags[n_w] (NULL = all 0), bit 0 is_dir, bit 1
+ *   SDGPU_IDX_ANCESTOR = the entry was pushed as an ancestor from a deeper
+ *   directory (walk.rs:560-617) and was in no listing of its own parent;
+ *   d_w_meta[n_w][3] = inode, device, modified_at (int64 ns since the epoch).
+ *   Walked directories: d_wd_key[n_wd], the children-path keys of the
+ *   directories whose listing was read; duplicates allowed.
+ *   file_path rows of the location in ascending id order: d_r_key[n_r];
+ *   d_r_dirkey[n_r] = the key of the row's own materialized_path; d_r_flags
+ *   [n_r] (NULL = all 0), bit 0 is_dir, bit 1 SDGPU_IDX_NO_METADATA = inode,
+ *   device or date_modified is NULL in the row (walk.rs:349-354); d_r_meta
+ *   [n_r][3] laid out as d_w_meta.
+ * For entry i let j0 = the lowest row with r_key == w_key[i]:
+ *   d_match[i] = j0, or SDGPU_IDX_MISS when no row has the key (written
+ *     whatever is_dir says, so the caller can check the pair's strings);
+ *   d_state[i] = 0 CREATE: no such row;
+ *                3 KIND_CHANGED: is_dir of row j0 differs from the entry's --
+ *                  the reference's HashMap is keyed by IsolatedFilePathData,
+ *                  whose Hash / Eq include is_dir (isolated_file_path_data.rs:
+ *                  25-38), so the entry misses it and is created;
+ *                2 UPDATE: same is_dir, row j0 has metadata, and inode differs,
+ *                  or device differs, or (int64)(w_mtime - r_mtime) > 1 000 000
+ *                  (one-sided, strict, signed, walk.rs:360-364: a row newer than
+ *                  the disk is left alone; the difference is taken in 64-bit
+ *                  two's complement);
+ *                1 UNCHANGED: otherwise, a matched NO_METADATA row included.
+ *   d_create = the entries of state 0 or 3, d_update those of state 2, both
+ *     ascending entry indices (capacity n_w each);
+ *   d_remove = ascending row indices j (capacity n_r) with r_dirkey[j] among
+ *     d_wd_key and no entry i with w_key[i] == r_key[j] whose ANCESTOR bit is
+ *     clear.  is_dir plays no part (the reference's found ids come from the
+ *     4-term query): a file replaced by a directory of the same name is created
+ *     (state 3) and NOT removed, as in the reference.  Rows of directories that
+ *     were not walked are never removed.
+ *   d_counts[4] = len(create), len(update), len(remove), entries of state 3.
+ * Nothing is written past the three lengths.  Duplicated keys (a caller error
+ * under the schema) stay defined: all rows of one key are spared or removed
+ * together, j0 answers for the key, every walked copy gets its own answer.
+ * The keys 0 and ~0 are ordinary keys on every side.  Any count may be 0.
+ * -EINVAL: a NULL required pointer with a non-zero count (d_match, d_state,
+ * d_create, d_update with n_w > 0; d_remove with n_r > 0; d_counts with any
+ * count > 0), a count >= 2^31.  The table of row keys in the context's
+ * workspace has 2 x n_r slots rounded up to a power of two, 2^31 at the most.
+ * Asynchronous on `stream`, no synchronisation. */
+#define SDGPU_IDX_ANCESTOR 2u
+#define SDGPU_IDX_NO_METADATA 2u
+#define SDGPU_IDX_MISS 0xFFFFFFFFu
+int sdgpu_indexer_diff_device(sdgpu_ctx *ctx, const uint64_t *d_w_key, const uint8_t *d_w_flags,
+                              const uint64_t *d_w_meta, uint64_t n_w, const uint64_t *d_wd_key,
+                              uint64_t n_wd, const uint64_t *d_r_key, const uint64_t *d_r_dirkey,
+                              const uint8_t *d_r_flags, const uint64_t *d_r_meta, uint64_t n_r,
+                              uint32_t *d_match, uint8_t *d_state, uint32_t *d_create,
+                              uint32_t *d_update, uint32_t *d_remove, uint32_t *d_counts,
+                              void *stream);
+/* (ABI 6, additive) The same on host arrays (what the indexer job calls with
+ * the rows it fetched and the entries it walked): copy in, run, copy out;
+ * returns when done.  Only counts[0..2] entries of the three lists travel
+ * back. */
+int sdgpu_indexer_diff(sdgpu_ctx *ctx, const uint64_t *w_key, const uint8_t *w_flags,
+                       const uint64_t *w_meta, uint64_t n_w, const uint64_t *wd_key,
+                       uint64_t n_wd, const uint64_t *r_key, const uint64_t *r_dirkey,
+                       const uint8_t *r_flags, const uint64_t *r_meta, uint64_t n_r,
+                       uint32_t *matched, uint8_t *state, uint32_t *create, uint32_t *update,
+                       uint32_t *remove, uint32_t *counts);
 
 /* ---- synthetic corpora (bench / tests; same content function as oracle/) ---- */
 int sdgpu_synth_cas_arena_device(sdgpu_ctx *ctx, const uint64_t *d_sizes, const uint64_t *d_seeds,

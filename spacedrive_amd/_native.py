@@ -132,6 +132,10 @@ def _proto(L):
                                                   c_vp, c_vp, c_vp, c_vp]),
         "sdgpu_thumbnail_worklist": (i32, [ctx, c_vp, u64, c_vp, c_vp, c_vp, u64, u32, c_vp, c_vp,
                                            c_vp, c_vp]),
+        "sdgpu_indexer_diff_device": (i32, [ctx, c_vp, c_vp, c_vp, u64, c_vp, u64, c_vp, c_vp, c_vp,
+                                            c_vp, u64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+        "sdgpu_indexer_diff": (i32, [ctx, c_vp, c_vp, c_vp, u64, c_vp, u64, c_vp, c_vp, c_vp, c_vp,
+                                     u64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
         "sdgpu_synth_vary_keys_device": (i32, [ctx, c_vp, c_vp, u64, u64, c_vp]),
         "sdgpu_set_timing": (i32, [ctx, i32]),
         "sdgpu_timing_reset": (i32, [ctx]),

@@ -394,6 +394,29 @@ hipError_t thumb_worklist_launch(const uint64_t* thumb_key, uint64_t n_thumbs, c
                                  uint32_t* stats, void* ws, void* group_ws, hipStream_t s,
                                  KTimer* timer = nullptr);
 
+// ---- indexer rescan diff (indexer.hip) ----------------------------------------------
+// The join of include/sdgpu.h (sdgpu_indexer_diff_device): walked entries and
+// walked directories of one location against its file_path rows.  ws:
+// indexer_workspace_bytes bytes, of which the call initialises all it reads.
+struct IndexerIn {
+  const uint64_t* w_key = nullptr;    // [n_w]
+  const uint8_t* w_flags = nullptr;   // [n_w] or null (all 0)
+  const uint64_t* w_meta = nullptr;   // [n_w][3] inode, device, modified_at
+  uint64_t n_w = 0;
+  const uint64_t* wd_key = nullptr;   // [n_wd]
+  uint64_t n_wd = 0;
+  const uint64_t* r_key = nullptr;    // [n_r]
+  const uint64_t* r_dirkey = nullptr; // [n_r]
+  const uint8_t* r_flags = nullptr;   // [n_r] or null (all 0)
+  const uint64_t* r_meta = nullptr;   // [n_r][3]
+  uint64_t n_r = 0;
+};
+size_t indexer_workspace_bytes(uint64_t n_w, uint64_t n_wd, uint64_t n_r);
+hipError_t indexer_diff_launch(const IndexerIn& in, uint32_t* match, uint8_t* state,
+                               uint32_t* create, uint32_t* update, uint32_t* remove,
+                               uint32_t* counts, void* ws, hipStream_t s,
+                               KTimer* timer = nullptr);
+
 // ---- Object link batch (K7) ----------------------------------------------------
 size_t link_workspace_bytes(uint64_t n);
 // rank may be null (rank = first_rank + i), valid may be null (all rows valid).

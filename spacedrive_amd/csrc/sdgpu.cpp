@@ -1813,6 +1813,109 @@ int sdgpu_thumbnail_worklist(sdgpu_ctx* c, const uint64_t* thumb_key, uint64_t n
   return 0;
 }
 
+// Indexer rescan diff (indexer.hip).  The checks both variants share.
+static bool indexer_args_ok(sdgpu_ctx* c, const IndexerIn& in, const uint32_t* matched,
+                            const uint8_t* state, const uint32_t* create, const uint32_t* update,
+                            const uint32_t* remove, const uint32_t* counts) {
+  if (!c || in.n_w >= (1ull << 31) || in.n_wd >= (1ull << 31) || in.n_r >= (1ull << 31))
+    return false;
+  if (in.n_w && (!in.w_key || !in.w_meta || !matched || !state || !create || !update)) return false;
+  if (in.n_wd && !in.wd_key) return false;
+  if (in.n_r && (!in.r_key || !in.r_dirkey || !in.r_meta || !remove)) return false;
+  return counts || !(in.n_w || in.n_wd || in.n_r);
+}
+
+int sdgpu_indexer_diff_device(sdgpu_ctx* c, const uint64_t* d_w_key, const uint8_t* d_w_flags,
+                              const uint64_t* d_w_meta, uint64_t n_w, const uint64_t* d_wd_key,
+                              uint64_t n_wd, const uint64_t* d_r_key, const uint64_t* d_r_dirkey,
+                              const uint8_t* d_r_flags, const uint64_t* d_r_meta, uint64_t n_r,
+                              uint32_t* d_match, uint8_t* d_state, uint32_t* d_create,
+                              uint32_t* d_update, uint32_t* d_remove, uint32_t* d_counts,
+                              void* stream) {
+  const IndexerIn in{d_w_key, d_w_flags, d_w_meta, n_w,       d_wd_key, n_wd,
+                     d_r_key, d_r_dirkey, d_r_flags, d_r_meta, n_r};
+  if (!indexer_args_ok(c, in, d_match, d_state, d_create, d_update, d_remove, d_counts))
+    return -EINVAL;
+  if (!d_counts) return 0;  // nothing on any side
+  std::lock_guard<std::mutex> g(c->mu);
+  SD_TRY(hipSetDevice(c->device));
+  hipStream_t s = pick(c, stream);
+  SD_TRY_RC(ensure_dev(c, c->link_ws, indexer_workspace_bytes(n_w, n_wd, n_r)));
+  SD_TRY(indexer_diff_launch(in, d_match, d_state, d_create, d_update, d_remove, d_counts,
+                             c->link_ws.p, s, c->kt()));
+  return 0;
+}
+
+int sdgpu_indexer_diff(sdgpu_ctx* c, const uint64_t* w_key, const uint8_t* w_flags,
+                       const uint64_t* w_meta, uint64_t n_w, const uint64_t* wd_key,
+                       uint64_t n_wd, const uint64_t* r_key, const uint64_t* r_dirkey,
+                       const uint8_t* r_flags, const uint64_t* r_meta, uint64_t n_r,
+                       uint32_t* matched, uint8_t* state, uint32_t* create, uint32_t* update,
+                       uint32_t* remove, uint32_t* counts) {
+  const IndexerIn hin{w_key, w_flags, w_meta, n_w,    wd_key, n_wd,
+                      r_key, r_dirkey, r_flags, r_meta, n_r};
+  if (!indexer_args_ok(c, hin, matched, state, create, update, remove, counts)) return -EINVAL;
+  if (n_w == 0 && n_r == 0) {  // three empty lists, decided on the host
+    if (counts) memset(counts, 0, 4 * 4);
+    return 0;
+  }
+  std::lock_guard<std::mutex> g(c->mu);
+  SD_TRY(hipSetDevice(c->device));
+  hipStream_t s = pick(c, nullptr);
+  // workspace | the inputs | matched, state, create, update, remove, counts in
+  // the context's link workspace
+  size_t o = align_up(indexer_workspace_bytes(n_w, n_wd, n_r), 256);
+  auto take = [&](size_t bytes) {
+    const size_t at = o;
+    o += align_up(bytes, 256);
+    return at;
+  };
+  const size_t o_wk = take(8 * n_w), o_wf = take(w_flags ? n_w : 0), o_wm = take(24 * n_w);
+  const size_t o_dk = take(8 * n_wd);
+  const size_t o_rk = take(8 * n_r), o_rd = take(8 * n_r), o_rf = take(r_flags ? n_r : 0);
+  const size_t o_rm = take(24 * n_r);
+  const size_t o_ma = take(4 * n_w), o_st = take(n_w), o_cr = take(4 * n_w), o_up = take(4 * n_w);
+  const size_t o_re = take(4 * n_r), o_cn = take(4 * 4);
+  SD_TRY_RC(ensure_dev(c, c->link_ws, o));
+  uint8_t* base = static_cast<uint8_t*>(c->link_ws.p);
+  auto u64p = [&](size_t at) { return reinterpret_cast<uint64_t*>(base + at); };
+  auto u32p = [&](size_t at) { return reinterpret_cast<uint32_t*>(base + at); };
+  if (n_w) {
+    SD_TRY(hipMemcpyAsync(base + o_wk, w_key, 8 * n_w, hipMemcpyHostToDevice, s));
+    if (w_flags) SD_TRY(hipMemcpyAsync(base + o_wf, w_flags, n_w, hipMemcpyHostToDevice, s));
+    SD_TRY(hipMemcpyAsync(base + o_wm, w_meta, 24 * n_w, hipMemcpyHostToDevice, s));
+  }
+  if (n_wd) SD_TRY(hipMemcpyAsync(base + o_dk, wd_key, 8 * n_wd, hipMemcpyHostToDevice, s));
+  if (n_r) {
+    SD_TRY(hipMemcpyAsync(base + o_rk, r_key, 8 * n_r, hipMemcpyHostToDevice, s));
+    SD_TRY(hipMemcpyAsync(base + o_rd, r_dirkey, 8 * n_r, hipMemcpyHostToDevice, s));
+    if (r_flags) SD_TRY(hipMemcpyAsync(base + o_rf, r_flags, n_r, hipMemcpyHostToDevice, s));
+    SD_TRY(hipMemcpyAsync(base + o_rm, r_meta, 24 * n_r, hipMemcpyHostToDevice, s));
+  }
+  const IndexerIn in{u64p(o_wk), w_flags ? base + o_wf : nullptr, u64p(o_wm), n_w,
+                     u64p(o_dk), n_wd,
+                     u64p(o_rk), u64p(o_rd), r_flags ? base + o_rf : nullptr, u64p(o_rm), n_r};
+  SD_TRY(indexer_diff_launch(in, u32p(o_ma), base + o_st, u32p(o_cr), u32p(o_up), u32p(o_re),
+                             u32p(o_cn), base, s, c->kt()));
+  SD_TRY(hipMemcpyAsync(counts, base + o_cn, 4 * 4, hipMemcpyDeviceToHost, s));
+  if (n_w) {
+    SD_TRY(hipMemcpyAsync(matched, base + o_ma, 4 * n_w, hipMemcpyDeviceToHost, s));
+    SD_TRY(hipMemcpyAsync(state, base + o_st, n_w, hipMemcpyDeviceToHost, s));
+  }
+  SD_TRY(hipStreamSynchronize(s));
+  // only the listed entries travel back
+  if (counts[0])
+    SD_TRY(hipMemcpy(create, base + o_cr, 4 * static_cast<size_t>(counts[0]),
+                     hipMemcpyDeviceToHost));
+  if (counts[1])
+    SD_TRY(hipMemcpy(update, base + o_up, 4 * static_cast<size_t>(counts[1]),
+                     hipMemcpyDeviceToHost));
+  if (counts[2])
+    SD_TRY(hipMemcpy(remove, base + o_re, 4 * static_cast<size_t>(counts[2]),
+                     hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int sdgpu_synth_vary_keys_device(sdgpu_ctx* c, uint64_t* d_key, const uint8_t* d_vary,
                                  uint64_t n, uint64_t step, void* stream) {
   if (!c || (n && (!d_key || !d_vary))) return -EINVAL;
