@@ -22,6 +22,7 @@
 
 pub mod burst;
 pub mod cas;
+pub mod explorer;
 pub mod hash;
 pub mod identifier;
 pub mod indexer;

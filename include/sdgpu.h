@@ -854,6 +854,163 @@ int sdgpu_indexer_diff(sdgpu_ctx *ctx, const uint64_t *w_key, const uint8_t *w_f
                        uint32_t *matched, uint8_t *state, uint32_t *create, uint32_t *update,
                        uint32_t *remove, uint32_t *counts);
 
+/* ---- explorer: one search page (ABI 6, additive) -------------------------------
+ * search.paths (core/src/api/search.rs:393-562), the query behind every folder
+ * view, category view and infinite scroll, over columns the caller keeps on the
+ * device: the WHERE clause over file_path and its Object (:127-187, :302-324),
+ * ORDER BY is_dir DESC, <field>, id (:429-431, :436-445, :477-478, :526-527), a
+ * keyset cursor (:446-528) or an offset (:439-445), take <= 100 (:421).  The
+ * count calls (pathsCount :563-582, objectsCount) are the same filter with
+ * take == 0; search.objects (:583-708) is the same call with the Object columns
+ * passed as the rows.  The per-item thumbnail_exists (:540-547) is the presence
+ * mode of the thumbnailer work list above.
+ *
+ * The three structs are plain host structs, read when the call is made; their
+ * array members are device pointers for the _device call, host pointers for the
+ * host call.  A column the query does not use may be NULL.
+ *
+ * Rows: one table's file_path rows in ascending id order; row index stands for
+ * id, as in the thumbnailer.  i64 values lie in (-2^62, 2^62), SDGPU_SEARCH_NULL
+ * is SQL NULL (nanosecond dates stay inside the range until the year 2116).
+ *
+ * Semantics: SQLite's three-valued logic, as the reference's Prisma client runs
+ * it -- a comparison with a NULL column value is false.
+ * Filter.  Row i matches iff eligible[i] != 0 (NULL pointer: every row; the
+ * caller's remaining WHERE terms, e.g. name contains, :165-169) and every term
+ * of `use` holds:
+ *   LOCATION      location[i] = location (:171)   EXTENSION  ext[i] = ext (:172)
+ *   CREATED_FROM  date_created[i] >= created_from (:173)
+ *   CREATED_TO    date_created[i] <= created_to (:174)
+ *   DIR           dir_key[i] = dir_key (materialized_path equals, :175-177)
+ * and on the row's Object o = object[i] (object::is(params), :178-182; any of
+ * these terms, or the flag NEEDS_OBJECT, fails a row with object[i] < 0 -- the
+ * default `hidden: Exclude` alone switches that on, :273-283):
+ *   HIDDEN_EXCLUDE  not (hidden is true): flags[o] bit 2 clear (:276-279)
+ *   FAVORITE        operand 1: flags[o] bit 0 set; operand 0: bits 0 (true) and
+ *                   1 (NULL) both clear (:310)
+ *   KIND            kind[o] not NULL and bit kind[o] of kind_mask set (:313;
+ *                   library/cat.rs:62-75)
+ *   TAGS            some pair (tag_obj, tag_tag) = (o, t) with t among
+ *                   tags[0..n_tags) (:314-319); duplicate pairs allowed
+ *   ACCESSED_EQ v   date_accessed[o] = v, or IS NULL when v is SDGPU_SEARCH_NULL
+ *   ACCESSED_NE v   date_accessed[o] <> v (false for a NULL column), or IS NOT
+ *                   NULL when v is SDGPU_SEARCH_NULL (:311-312, cat.rs:64)
+ * Candidates.  A matching row is a candidate iff it passes FILES_ONLY (bit 0 of
+ * flags[i] clear, :453-455) and the cursor predicate: true without CURSOR; with
+ * CURSOR and no order key, i >= cursor_row (:483-485); with an order key v and
+ * cursor_key c, a NULL v fails, and otherwise
+ *   ascending   v > c, or (without CURSOR_STRICT) v == c and i >= cursor_row;
+ *   descending  v < c, or (without CURSOR_STRICT) v == c and i <  cursor_row
+ * (:463-475).  The caller turns the cursor's id into cursor_row: the number of
+ * rows with id <= it when ascending, with id < it when descending.  The order
+ * key is order_key[i], or with ORDER_BY_OBJECT objects->order_key[object[i]]
+ * (NULL for a row with no Object); a NULL order_key pointer = no order field.
+ * Order.  Directories first under GROUP_DIRS, in both directions (:429-431);
+ * then the order key, NULL lowest (first ascending, last descending, SQLite's
+ * rule); then ascending row index, always.
+ * Outputs.  d_page[0..P) = the candidates of ranks [offset, offset + take) in
+ * that order, nothing is written past P; d_counts[4] = matching rows
+ * (pathsCount), candidates, P = min(take, max(0, candidates - offset)),
+ * directories among the matching rows (0 when rows->flags is NULL).  take == 0
+ * is the count call, d_page may then be NULL.
+ * Kept from the reference: the cursor predicate applies to directories and
+ * files alike (:453-479); descending ties compare id < while the order stays id
+ * ascending (:472, :526-527); the Object-field cursors have no tie arm
+ * (:497-515) -- CURSOR_STRICT; NULL-keyed rows are never reached through a
+ * cursor.  Deviation: where the reference gives no final id order (OrderOnly
+ * and Offset, :436-445) SQLite's tie order is unspecified; here ties are
+ * always ascending id, one of the orders SQLite may return.
+ * Exactness: dir_key is a 64-bit stand-in (the indexer's r_dirkey); the caller
+ * string-checks the at most SDGPU_SEARCH_MAX_TAKE returned rows, as the
+ * indexer's caller checks its matched pairs.
+ * The selection is exact and sorts at most SDGPU_SEARCH_SELECT_FINAL records,
+ * whatever offset is.
+ * -EINVAL: NULL ctx, rows, query or d_counts; take > SDGPU_SEARCH_MAX_TAKE;
+ * d_page NULL with take > 0; CURSOR together with a non-zero offset;
+ * CURSOR_STRICT without CURSOR; ORDER_BY_OBJECT without objects; n_tags > 32;
+ * an unknown bit in `use` or `flags`; a column the query uses that is NULL
+ * (rows->flags with GROUP_DIRS or FILES_ONLY; rows->object with any Object
+ * term, NEEDS_OBJECT or ORDER_BY_OBJECT; `objects` and its column with an
+ * Object term; the pair arrays with TAGS and n_pairs > 0); n, m or n_pairs >=
+ * 2^31; negative offset.  n == 0: zeros in d_counts.  Asynchronous on
+ * `stream`, no synchronisation. */
+#define SDGPU_SEARCH_MAX_TAKE 256u
+#define SDGPU_SEARCH_SELECT_FINAL 3840u
+#define SDGPU_SEARCH_NULL (-(INT64_C(1) << 62))
+#define SDGPU_SEARCH_USE_LOCATION 0x1u
+#define SDGPU_SEARCH_USE_EXTENSION 0x2u
+#define SDGPU_SEARCH_USE_CREATED_FROM 0x4u
+#define SDGPU_SEARCH_USE_CREATED_TO 0x8u
+#define SDGPU_SEARCH_USE_DIR 0x10u
+#define SDGPU_SEARCH_USE_FAVORITE 0x20u
+#define SDGPU_SEARCH_USE_HIDDEN_EXCLUDE 0x40u
+#define SDGPU_SEARCH_USE_KIND 0x80u
+#define SDGPU_SEARCH_USE_TAGS 0x100u
+#define SDGPU_SEARCH_USE_ACCESSED_EQ 0x200u
+#define SDGPU_SEARCH_USE_ACCESSED_NE 0x400u
+#define SDGPU_SEARCH_DESC 0x1u
+#define SDGPU_SEARCH_GROUP_DIRS 0x2u
+#define SDGPU_SEARCH_FILES_ONLY 0x4u
+#define SDGPU_SEARCH_CURSOR 0x8u
+#define SDGPU_SEARCH_CURSOR_STRICT 0x10u
+#define SDGPU_SEARCH_ORDER_BY_OBJECT 0x20u
+#define SDGPU_SEARCH_NEEDS_OBJECT 0x40u
+typedef struct sdgpu_search_rows_t {
+  uint64_t n;
+  const int32_t *location;     /* [n] -1 = NULL */
+  const uint16_t *ext;         /* [n] id in the caller's dictionary of extension strings,
+                                  0xFFFF = NULL */
+  const uint64_t *dir_key;     /* [n] key of the row's materialized_path (r_dirkey) */
+  const uint8_t *flags;        /* [n] bit 0 = is_dir is true */
+  const int64_t *date_created; /* [n] */
+  const int32_t *object;       /* [n] index into the Object columns, -1 = no Object */
+  const uint8_t *eligible;     /* [n] NULL = every row */
+  const int64_t *order_key;    /* [n] the column the query orders by: a date, the size, a
+                                  rank of the name under the database's collation */
+} sdgpu_search_rows_t;
+typedef struct sdgpu_search_objects_t {
+  uint64_t m;
+  const int32_t *kind;          /* [m] -1 = NULL */
+  const uint8_t *flags;         /* [m] bit 0 favorite is true, bit 1 favorite is NULL,
+                                   bit 2 hidden is true */
+  const int64_t *date_accessed; /* [m] */
+  const int64_t *order_key;     /* [m] */
+  const int32_t *tag_obj;       /* [n_pairs] the tag_on_object pairs */
+  const int32_t *tag_tag;       /* [n_pairs] */
+  uint64_t n_pairs;
+} sdgpu_search_objects_t;
+typedef struct sdgpu_search_query_t {
+  uint32_t use;      /* SDGPU_SEARCH_USE_* */
+  uint32_t flags;    /* SDGPU_SEARCH_DESC ... _NEEDS_OBJECT */
+  int32_t location;
+  uint16_t ext;
+  uint16_t favorite; /* 0 / 1 */
+  uint64_t dir_key;
+  int64_t created_from;
+  int64_t created_to;
+  uint32_t kind_mask; /* bit = ObjectKind value */
+  uint32_t n_tags;
+  int32_t tags[32];
+  int64_t accessed_eq;
+  int64_t accessed_ne;
+  int64_t cursor_key;
+  int64_t cursor_row;
+  int64_t offset;
+  uint32_t take;
+  uint32_t reserved; /* 0 */
+} sdgpu_search_query_t;
+int sdgpu_search_page_device(sdgpu_ctx *ctx, const sdgpu_search_rows_t *rows,
+                             const sdgpu_search_objects_t *objects,
+                             const sdgpu_search_query_t *query, uint32_t *d_page,
+                             uint32_t *d_counts, void *stream);
+/* (ABI 6, additive) The same on host arrays (what the explorer's rspc handler
+ * calls with columns it holds in memory): copy in the columns the query uses,
+ * run, copy back counts and only counts[2] entries of page; returns when done.
+ * n == 0 is decided without a device. */
+int sdgpu_search_page(sdgpu_ctx *ctx, const sdgpu_search_rows_t *rows,
+                      const sdgpu_search_objects_t *objects, const sdgpu_search_query_t *query,
+                      uint32_t *page, uint32_t *counts);
+
 /* ---- synthetic corpora (bench / tests; same content function as oracle/) ---- */
 int sdgpu_synth_cas_arena_device(sdgpu_ctx *ctx, const uint64_t *d_sizes, const uint64_t *d_seeds,
                                  const uint64_t *d_off, uint32_t n, uint8_t *d_arena, void *stream);

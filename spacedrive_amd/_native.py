@@ -136,6 +136,8 @@ def _proto(L):
                                             c_vp, u64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
         "sdgpu_indexer_diff": (i32, [ctx, c_vp, c_vp, c_vp, u64, c_vp, u64, c_vp, c_vp, c_vp, c_vp,
                                      u64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+        "sdgpu_search_page_device": (i32, [ctx, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+        "sdgpu_search_page": (i32, [ctx, c_vp, c_vp, c_vp, c_vp, c_vp]),
         "sdgpu_synth_vary_keys_device": (i32, [ctx, c_vp, c_vp, u64, u64, c_vp]),
         "sdgpu_set_timing": (i32, [ctx, i32]),
         "sdgpu_timing_reset": (i32, [ctx]),

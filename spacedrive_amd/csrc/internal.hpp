@@ -8,6 +8,11 @@
 
 #include "tree_plan.hpp"
 
+// the explorer's argument structs (include/sdgpu.h)
+struct sdgpu_search_rows_t;
+struct sdgpu_search_objects_t;
+struct sdgpu_search_query_t;
+
 namespace sdgpu {
 
 // Optional per-kernel timing: the C-ABI layer passes a recorder that brackets
@@ -416,6 +421,18 @@ hipError_t indexer_diff_launch(const IndexerIn& in, uint32_t* match, uint8_t* st
                                uint32_t* create, uint32_t* update, uint32_t* remove,
                                uint32_t* counts, void* ws, hipStream_t s,
                                KTimer* timer = nullptr);
+
+// ---- explorer search page (search.hip) -----------------------------------------------
+// The query of include/sdgpu.h (sdgpu_search_page_device) on device columns: tag
+// marks, filter + candidate records, radix select, final LDS sort.  ws:
+// search_workspace_bytes bytes (36 per row for the candidates and the passes' two
+// buffers, one per Object, 148 KiB of control), of which the call initialises
+// all it reads.  The arguments are already checked.
+size_t search_workspace_bytes(uint64_t n, uint64_t m);
+hipError_t search_page_launch(const sdgpu_search_rows_t& rows,
+                              const sdgpu_search_objects_t* objects,
+                              const sdgpu_search_query_t& query, uint32_t* page, uint32_t* counts,
+                              void* ws, hipStream_t s, KTimer* timer = nullptr);
 
 // ---- Object link batch (K7) ----------------------------------------------------
 size_t link_workspace_bytes(uint64_t n);

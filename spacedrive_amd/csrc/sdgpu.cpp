@@ -1916,6 +1916,149 @@ int sdgpu_indexer_diff(sdgpu_ctx* c, const uint64_t* w_key, const uint8_t* w_fla
   return 0;
 }
 
+// Explorer search page (search.hip).  The columns a query reads; the checks
+// both variants share.
+struct SearchNeed {
+  bool location, ext, dir_key, flags, date_created, object, eligible, order_key;
+  bool objects, kind, oflags, date_accessed, o_order_key, pairs;
+};
+
+static bool search_args_ok(sdgpu_ctx* c, const sdgpu_search_rows_t* r,
+                           const sdgpu_search_objects_t* o, const sdgpu_search_query_t* q,
+                           const uint32_t* page, const uint32_t* counts, SearchNeed* need) {
+  constexpr uint32_t kUse = 0x7FFu, kFlags = 0x7Fu;
+  constexpr uint32_t kObjTerms = SDGPU_SEARCH_USE_FAVORITE | SDGPU_SEARCH_USE_HIDDEN_EXCLUDE |
+                                 SDGPU_SEARCH_USE_KIND | SDGPU_SEARCH_USE_TAGS |
+                                 SDGPU_SEARCH_USE_ACCESSED_EQ | SDGPU_SEARCH_USE_ACCESSED_NE;
+  if (!c || !r || !q || !counts) return false;
+  if ((q->use & ~kUse) || (q->flags & ~kFlags)) return false;
+  if (q->take > SDGPU_SEARCH_MAX_TAKE || (q->take && !page) || q->offset < 0) return false;
+  if ((q->flags & SDGPU_SEARCH_CURSOR) && q->offset != 0) return false;
+  if ((q->flags & SDGPU_SEARCH_CURSOR_STRICT) && !(q->flags & SDGPU_SEARCH_CURSOR)) return false;
+  if ((q->flags & SDGPU_SEARCH_ORDER_BY_OBJECT) && !o) return false;
+  if (q->n_tags > 32) return false;
+  if (r->n >= (1ull << 31) || (o && (o->m >= (1ull << 31) || o->n_pairs >= (1ull << 31))))
+    return false;
+  SearchNeed n{};
+  const uint32_t use = q->use, fl = q->flags;
+  n.location = use & SDGPU_SEARCH_USE_LOCATION;
+  n.ext = use & SDGPU_SEARCH_USE_EXTENSION;
+  n.dir_key = use & SDGPU_SEARCH_USE_DIR;
+  n.date_created = use & (SDGPU_SEARCH_USE_CREATED_FROM | SDGPU_SEARCH_USE_CREATED_TO);
+  n.objects = (use & kObjTerms) || (fl & SDGPU_SEARCH_ORDER_BY_OBJECT);
+  n.object = n.objects || (fl & SDGPU_SEARCH_NEEDS_OBJECT);
+  n.kind = use & SDGPU_SEARCH_USE_KIND;
+  n.oflags = use & (SDGPU_SEARCH_USE_FAVORITE | SDGPU_SEARCH_USE_HIDDEN_EXCLUDE);
+  n.date_accessed = use & (SDGPU_SEARCH_USE_ACCESSED_EQ | SDGPU_SEARCH_USE_ACCESSED_NE);
+  n.o_order_key = fl & SDGPU_SEARCH_ORDER_BY_OBJECT;
+  n.pairs = (use & SDGPU_SEARCH_USE_TAGS) && o && o->n_pairs;
+  if (n.objects && !o) return false;
+  if (r->n) {
+    if ((n.location && !r->location) || (n.ext && !r->ext) || (n.dir_key && !r->dir_key) ||
+        (n.date_created && !r->date_created) || (n.object && !r->object))
+      return false;
+    if ((fl & (SDGPU_SEARCH_GROUP_DIRS | SDGPU_SEARCH_FILES_ONLY)) && !r->flags) return false;
+    if (o && o->m &&
+        ((n.kind && !o->kind) || (n.oflags && !o->flags) ||
+         (n.date_accessed && !o->date_accessed) || (n.o_order_key && !o->order_key)))
+      return false;
+    if (n.pairs && (!o->tag_obj || !o->tag_tag)) return false;
+  }
+  // optional columns travel when they are there
+  n.flags = r->flags != nullptr;
+  n.eligible = r->eligible != nullptr;
+  n.order_key = r->order_key != nullptr && !n.o_order_key;
+  if (need) *need = n;
+  return true;
+}
+
+int sdgpu_search_page_device(sdgpu_ctx* c, const sdgpu_search_rows_t* rows,
+                             const sdgpu_search_objects_t* objects,
+                             const sdgpu_search_query_t* query, uint32_t* d_page,
+                             uint32_t* d_counts, void* stream) {
+  if (!search_args_ok(c, rows, objects, query, d_page, d_counts, nullptr)) return -EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  SD_TRY(hipSetDevice(c->device));
+  hipStream_t s = pick(c, stream);
+  SD_TRY_RC(ensure_dev(c, c->link_ws, search_workspace_bytes(rows->n, objects ? objects->m : 0)));
+  SD_TRY(search_page_launch(*rows, objects, *query, d_page, d_counts, c->link_ws.p, s, c->kt()));
+  return 0;
+}
+
+int sdgpu_search_page(sdgpu_ctx* c, const sdgpu_search_rows_t* rows,
+                      const sdgpu_search_objects_t* objects, const sdgpu_search_query_t* query,
+                      uint32_t* page, uint32_t* counts) {
+  SearchNeed need;
+  if (!search_args_ok(c, rows, objects, query, page, counts, &need)) return -EINVAL;
+  if (rows->n == 0) {  // decided on the host
+    memset(counts, 0, 4 * 4);
+    return 0;
+  }
+  std::lock_guard<std::mutex> g(c->mu);
+  SD_TRY(hipSetDevice(c->device));
+  hipStream_t s = pick(c, nullptr);
+  const uint64_t n = rows->n, m = objects ? objects->m : 0;
+  const uint64_t np = need.pairs ? objects->n_pairs : 0;
+  // workspace | the columns the query uses | page, counts in the context's link
+  // workspace
+  size_t o = align_up(search_workspace_bytes(n, m), 256);
+  auto take = [&](bool on, size_t bytes) {
+    const size_t at = o;
+    if (on) o += align_up(bytes, 256);
+    return at;
+  };
+  const size_t o_loc = take(need.location, 4 * n), o_ext = take(need.ext, 2 * n);
+  const size_t o_dir = take(need.dir_key, 8 * n), o_fl = take(need.flags, n);
+  const size_t o_dc = take(need.date_created, 8 * n), o_obj = take(need.object, 4 * n);
+  const size_t o_el = take(need.eligible, n), o_ok = take(need.order_key, 8 * n);
+  const size_t o_kind = take(need.kind, 4 * m), o_ofl = take(need.oflags, m);
+  const size_t o_da = take(need.date_accessed, 8 * m), o_ook = take(need.o_order_key, 8 * m);
+  const size_t o_to = take(need.pairs, 4 * np), o_tt = take(need.pairs, 4 * np);
+  const size_t o_page = take(true, 4 * SDGPU_SEARCH_MAX_TAKE), o_cnt = take(true, 4 * 4);
+  SD_TRY_RC(ensure_dev(c, c->link_ws, o));
+  uint8_t* base = static_cast<uint8_t*>(c->link_ws.p);
+  sdgpu_search_rows_t dr{};
+  sdgpu_search_objects_t dobj{};
+  dr.n = n;
+  dobj.m = m;
+  dobj.n_pairs = np;
+  // the copy is enqueued only for a column that is there: `at` is then its own
+  hipError_t up_err = hipSuccess;
+  auto up = [&](bool on, size_t at, const void* src, size_t bytes) -> const void* {
+    if (!on || !src || !bytes || up_err != hipSuccess) return nullptr;
+    up_err = hipMemcpyAsync(base + at, src, bytes, hipMemcpyHostToDevice, s);
+    return base + at;
+  };
+#define SD_COL(T, on, at, src, bytes) static_cast<const T*>(up(on, at, src, bytes))
+  dr.location = SD_COL(int32_t, need.location, o_loc, rows->location, 4 * n);
+  dr.ext = SD_COL(uint16_t, need.ext, o_ext, rows->ext, 2 * n);
+  dr.dir_key = SD_COL(uint64_t, need.dir_key, o_dir, rows->dir_key, 8 * n);
+  dr.flags = SD_COL(uint8_t, need.flags, o_fl, rows->flags, n);
+  dr.date_created = SD_COL(int64_t, need.date_created, o_dc, rows->date_created, 8 * n);
+  dr.object = SD_COL(int32_t, need.object, o_obj, rows->object, 4 * n);
+  dr.eligible = SD_COL(uint8_t, need.eligible, o_el, rows->eligible, n);
+  dr.order_key = SD_COL(int64_t, need.order_key, o_ok, rows->order_key, 8 * n);
+  if (objects) {
+    dobj.kind = SD_COL(int32_t, need.kind, o_kind, objects->kind, 4 * m);
+    dobj.flags = SD_COL(uint8_t, need.oflags, o_ofl, objects->flags, m);
+    dobj.date_accessed = SD_COL(int64_t, need.date_accessed, o_da, objects->date_accessed, 8 * m);
+    dobj.order_key = SD_COL(int64_t, need.o_order_key, o_ook, objects->order_key, 8 * m);
+    dobj.tag_obj = SD_COL(int32_t, need.pairs, o_to, objects->tag_obj, 4 * np);
+    dobj.tag_tag = SD_COL(int32_t, need.pairs, o_tt, objects->tag_tag, 4 * np);
+  }
+#undef SD_COL
+  SD_TRY(up_err);
+  uint32_t* dpage = reinterpret_cast<uint32_t*>(base + o_page);
+  uint32_t* dcnt = reinterpret_cast<uint32_t*>(base + o_cnt);
+  SD_TRY(search_page_launch(dr, objects ? &dobj : nullptr, *query, dpage, dcnt, base, s, c->kt()));
+  SD_TRY(hipMemcpyAsync(counts, dcnt, 4 * 4, hipMemcpyDeviceToHost, s));
+  SD_TRY(hipStreamSynchronize(s));
+  // only the page's rows travel back
+  if (counts[2])
+    SD_TRY(hipMemcpy(page, dpage, 4 * static_cast<size_t>(counts[2]), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int sdgpu_synth_vary_keys_device(sdgpu_ctx* c, uint64_t* d_key, const uint8_t* d_vary,
                                  uint64_t n, uint64_t step, void* stream) {
   if (!c || (n && (!d_key || !d_vary))) return -EINVAL;
