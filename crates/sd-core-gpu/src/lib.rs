@@ -11,6 +11,8 @@
 //!   -- core/src/object/media/thumbnail/mod.rs:204-359 (`thumbnailer.rs` here)
 //! * the indexer's rescan diff (to_create / to_update / to_remove)
 //!   -- core/src/location/indexer/walk.rs:309-381,624-636 (`indexer.rs` here)
+//! * sync ingest: which CRDT operations of a page apply
+//!   -- core/crates/sync/src/ingest.rs:114-233 (`sync.rs` here)
 //!
 //! Blocking library calls run inside `spawn_blocking`, as the reference's
 //! `tokio::fs` calls do, so the async runtime never blocks.  Errors are the
@@ -27,6 +29,7 @@ pub mod hash;
 pub mod identifier;
 pub mod indexer;
 pub mod job;
+pub mod sync;
 pub mod thumbnail_remover;
 pub mod thumbnailer;
 

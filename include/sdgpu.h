@@ -854,6 +854,98 @@ int sdgpu_indexer_diff(sdgpu_ctx *ctx, const uint64_t *w_key, const uint8_t *w_f
                        uint32_t *matched, uint8_t *state, uint32_t *create, uint32_t *update,
                        uint32_t *remove, uint32_t *counts);
 
+/* ---- sync ingest: which CRDT operations apply (ABI 6, additive) -----------------
+ * The receiving half of library sync, core/crates/sync/src/ingest.rs.
+ * receive_crdt_operation (ingest.rs:114-160) handles one op at a time, strictly
+ * in page order (ingest.rs:67-71; pages of 1000 ops, core/src/p2p/sync/mod.rs:
+ * 403-431).  For each op compare_message (ingest.rs:188-233) finds the newest
+ * op of shared_operation / relation_operation (core/prisma/schema.prisma:21-53)
+ * with timestamp >= t and the op's (model, record_id, kind) or (relation,
+ * item_id, kind) -- group_id plays no part (ingest.rs:213-220); kind is "c",
+ * "u:<field>" or "d" (crates/sync/src/crdt.rs:9-23,34-36,67-69) -- and the op is
+ * old exactly when one exists and its timestamp != t.  With L(k) the largest
+ * logged timestamp of key k in SIGNED int64 order (an NTP64 stored
+ * `as_u64() as i64`, compared as SQLite compares the BigInt column):
+ *     old  <=>  L(k) > t;   an equal timestamp is not old (a re-delivered op is
+ *     applied again).
+ * An op that is not old is applied and logged (apply_op, ingest.rs:162-186), so
+ * later ops of the page see it; an old op lies below the running maximum.  Hence
+ *     apply[i] = ( t[i] >= max( L(key[i]), max{ t[j] : j < i, key[j] == key[i] } ) )
+ * Old or not, the instance's clock becomes max(clock or t, t) in UNSIGNED NTP64
+ * order (ingest.rs:119-126,151).  An absent L equals INT64_MIN and an absent
+ * clock 0; neither sentinel changes any answer.  get_ops (manager.rs:130-199),
+ * the writes of apply_op, the HLC and the transport stay with the caller.
+ *
+ * A key is 64 bits of BLAKE3 of the tuple (the reference compares the strings);
+ * a tag is a second, independent 64-bit hash of the same tuple (a caller that
+ * has none passes the key).  The thread that enters a key into the log stores
+ * its tag; every other op of that key, in this call or any later one, compares
+ * its tag with the stored one, and the disagreements are counted.  A non-zero
+ * count means two tuples share a key and the answers for them are not the
+ * reference's: the caller re-keys with another salt and reloads the log.  The
+ * case is detected, not repaired.
+ *
+ * sdgpu_oplog: key -> newest logged timestamp; lives as long as the library.
+ * Open addressing, 32-byte slots, load <= 1/2, at most 2^31 slots (-ENOSPC
+ * beyond).  The handle belongs to `ctx` and must be destroyed before it. */
+typedef struct sdgpu_oplog sdgpu_oplog;
+/* (ABI 6, additive) capacity_hint: keys expected (<= 2^30; the log grows). */
+int sdgpu_oplog_create(sdgpu_ctx *ctx, uint64_t capacity_hint, sdgpu_oplog **out);
+/* (ABI 6, additive) */
+int sdgpu_oplog_destroy(sdgpu_oplog *log);
+/* (ABI 6, additive) Forgets every key; the capacity stays. */
+int sdgpu_oplog_clear(sdgpu_oplog *log, void *stream);
+/* (ABI 6, additive) out = {keys stored, capacity in slots}; synchronises. */
+int sdgpu_oplog_stats(sdgpu_oplog *log, uint64_t out[2]);
+/* (ABI 6, additive) Loads existing op-log rows (what compare_message's
+ * find_first would scan, ingest.rs:188-233): L(key) = max(L(key), ts) in signed
+ * order; the order of the rows does not matter.  d_collisions (device, may be
+ * NULL) = the rows whose tag is not the one stored with their key.  -EINVAL: a
+ * NULL d_key, d_tag or d_ts with n > 0, n >= 2^31.  May synchronise `stream`
+ * when the table grows; otherwise asynchronous. */
+int sdgpu_oplog_add_device(sdgpu_oplog *log, const uint64_t *d_key, const uint64_t *d_tag,
+                           const int64_t *d_ts, uint64_t n, uint32_t *d_collisions, void *stream);
+/* (ABI 6, additive) d_ts[i] = L(d_key[i]) and d_found[i] = 1 (ingest.rs:188-233
+ * asks for the same row); for a key that is absent or holds no timestamp yet
+ * INT64_MIN and 0 -- a logged op at INT64_MIN reads the same way, which changes
+ * no decision.  A pure read: no growth, asynchronous. */
+int sdgpu_oplog_latest_device(sdgpu_oplog *log, const uint64_t *d_key, uint64_t n,
+                              int64_t *d_ts, uint8_t *d_found, void *stream);
+/* (ABI 6, additive) One page of ops in arrival order (ingest.rs:114-160, the
+ * rule above):
+ *   d_apply[i] = 1 when op i applies, else 0;
+ *   d_applied  = the ascending indices with apply == 1 (capacity n);
+ *   d_winner   = the ascending indices of the highest-index applied op of every
+ *                key that has one -- the only ops whose value survives in the
+ *                row (capacity n);
+ *   d_counts[4] = applied, winners, keys new to the log, tag disagreements.
+ * Nothing is written past the two list lengths.  Afterwards L(k) includes every
+ * applied op (ingest.rs:162-186).  SDGPU_INGEST_NO_COMMIT: the same decisions,
+ * in-page visibility included, but no timestamp in the log changes (the page's
+ * keys may still be entered, with no timestamp); the caller commits later with
+ * sdgpu_oplog_add_device.
+ *   d_clock[d_instance[i]] = max_u64(old, (uint64_t)d_ts[i]) for every op
+ * (ingest.rs:119-126,151); an index >= n_instances updates nothing; d_instance
+ * and d_clock may both be NULL with n_instances == 0.
+ * The keys 0 and ~0 are ordinary keys.  n == 0 zeroes the counts.  -EINVAL: a
+ * NULL required pointer with n > 0, n >= 2^31, unknown flag bits, exactly one of
+ * d_instance / d_clock given.  May synchronise `stream` when the table grows, as
+ * sdgpu_index_* does; otherwise asynchronous, no synchronisation. */
+#define SDGPU_INGEST_NO_COMMIT 1u
+int sdgpu_sync_ingest_device(sdgpu_oplog *log, const uint64_t *d_key, const uint64_t *d_tag,
+                             const int64_t *d_ts, const uint32_t *d_instance, uint64_t n,
+                             uint64_t *d_clock, uint32_t n_instances, uint32_t flags,
+                             uint8_t *d_apply, uint32_t *d_applied, uint32_t *d_winner,
+                             uint32_t *d_counts, void *stream);
+/* (ABI 6, additive) The same on host arrays (what the actor's Ingesting state,
+ * ingest.rs:67-71, calls with a received page): copy in, run, copy out; returns
+ * when done.  Only counts[0] / counts[1] entries of the two lists travel back.
+ * n == 0 is decided without a device. */
+int sdgpu_sync_ingest(sdgpu_oplog *log, const uint64_t *key, const uint64_t *tag,
+                      const int64_t *ts, const uint32_t *instance, uint64_t n, uint64_t *clock,
+                      uint32_t n_instances, uint32_t flags, uint8_t *apply, uint32_t *applied,
+                      uint32_t *winner, uint32_t *counts);
+
 /* ---- explorer: one search page (ABI 6, additive) -------------------------------
  * search.paths (core/src/api/search.rs:393-562), the query behind every folder
  * view, category view and infinite scroll, over columns the caller keeps on the

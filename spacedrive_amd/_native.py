@@ -136,6 +136,16 @@ def _proto(L):
                                             c_vp, u64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
         "sdgpu_indexer_diff": (i32, [ctx, c_vp, c_vp, c_vp, u64, c_vp, u64, c_vp, c_vp, c_vp, c_vp,
                                      u64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+        "sdgpu_oplog_create": (i32, [ctx, u64, P(c_vp)]),
+        "sdgpu_oplog_destroy": (i32, [c_vp]),
+        "sdgpu_oplog_clear": (i32, [c_vp, c_vp]),
+        "sdgpu_oplog_stats": (i32, [c_vp, P(ctypes.c_uint64)]),
+        "sdgpu_oplog_add_device": (i32, [c_vp, c_vp, c_vp, c_vp, u64, c_vp, c_vp]),
+        "sdgpu_oplog_latest_device": (i32, [c_vp, c_vp, u64, c_vp, c_vp, c_vp]),
+        "sdgpu_sync_ingest_device": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, u64, c_vp, u32, u32, c_vp,
+                                           c_vp, c_vp, c_vp, c_vp]),
+        "sdgpu_sync_ingest": (i32, [c_vp, c_vp, c_vp, c_vp, c_vp, u64, c_vp, u32, u32, c_vp, c_vp,
+                                    c_vp, c_vp]),
         "sdgpu_search_page_device": (i32, [ctx, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
         "sdgpu_search_page": (i32, [ctx, c_vp, c_vp, c_vp, c_vp, c_vp]),
         "sdgpu_synth_vary_keys_device": (i32, [ctx, c_vp, c_vp, u64, u64, c_vp]),

@@ -12,6 +12,8 @@
 struct sdgpu_search_rows_t;
 struct sdgpu_search_objects_t;
 struct sdgpu_search_query_t;
+// the op log's handle (include/sdgpu.h; defined in shard.cpp)
+struct sdgpu_oplog;
 
 namespace sdgpu {
 
@@ -433,6 +435,53 @@ hipError_t search_page_launch(const sdgpu_search_rows_t& rows,
                               const sdgpu_search_objects_t* objects,
                               const sdgpu_search_query_t& query, uint32_t* page, uint32_t* counts,
                               void* ws, hipStream_t s, KTimer* timer = nullptr);
+
+// ---- sync ingest (sync.hip) ------------------------------------------------------------
+// The op log of include/sdgpu.h (sdgpu_oplog): key -> newest logged timestamp.
+struct OplogRef {
+  uint64_t* slots = nullptr;            // [cap + 1][4] {key, timestamp ^ 1 << 63, tag, spare};
+                                        // [cap]: the key ~0 (key word 0 once entered)
+  uint64_t cap = 0;                     // power of two, at most 2^31
+  unsigned long long* count = nullptr;  // keys stored, the key ~0 not counted (device)
+};
+// 8-bit digits of a slot number 0 .. cap: the passes of the ingest's sort.
+uint32_t oplog_sort_passes(uint64_t cap);
+hipError_t oplog_clear_launch(const OplogRef& t, hipStream_t s);
+// clears `to`, then enters every key of `from` with its timestamp and tag
+hipError_t oplog_rehash_launch(const OplogRef& from, const OplogRef& to, hipStream_t s);
+// The three calls below never meet a full table: the caller reserved room for
+// n more keys.  collisions (device, may be null) = ops whose tag is not the
+// one stored with their key; ws: oplog_add_workspace_bytes bytes.
+size_t oplog_add_workspace_bytes(uint64_t n, bool collisions);
+hipError_t oplog_add_launch(const OplogRef& t, const uint64_t* key, const uint64_t* tag,
+                            const int64_t* ts, uint64_t n, uint32_t* collisions, void* ws,
+                            hipStream_t s, KTimer* timer = nullptr);
+hipError_t oplog_latest_launch(const OplogRef& t, const uint64_t* key, uint64_t n, int64_t* ts,
+                               uint8_t* found, hipStream_t s, KTimer* timer = nullptr);
+// sdgpu_sync_ingest_device on checked arguments.  ws: sync_ingest_workspace_bytes
+// bytes (29 per op and 1 KiB per 2048 ops of counts), of which the call
+// initialises all it reads.  instance / clock both null or both given.
+size_t sync_ingest_workspace_bytes(uint64_t n);
+hipError_t sync_ingest_launch(const OplogRef& t, const uint64_t* key, const uint64_t* tag,
+                              const int64_t* ts, const uint32_t* instance, uint64_t n,
+                              uint64_t* clock, uint32_t n_instances, bool commit, uint8_t* apply,
+                              uint32_t* applied, uint32_t* winner, uint32_t* counts, void* ws,
+                              hipStream_t s, KTimer* timer = nullptr);
+
+// The entry points on checked arguments (shard.cpp, beside the handle; the
+// checks are sdgpu.cpp's).  n > 0 on the host variant.
+int oplog_add_run(sdgpu_oplog* x, const uint64_t* d_key, const uint64_t* d_tag,
+                  const int64_t* d_ts, uint64_t n, uint32_t* d_collisions, void* stream);
+int oplog_latest_run(sdgpu_oplog* x, const uint64_t* d_key, uint64_t n, int64_t* d_ts,
+                     uint8_t* d_found, void* stream);
+int sync_ingest_run(sdgpu_oplog* x, const uint64_t* d_key, const uint64_t* d_tag,
+                    const int64_t* d_ts, const uint32_t* d_instance, uint64_t n, uint64_t* d_clock,
+                    uint32_t n_instances, uint32_t flags, uint8_t* d_apply, uint32_t* d_applied,
+                    uint32_t* d_winner, uint32_t* d_counts, void* stream);
+int sync_ingest_host_run(sdgpu_oplog* x, const uint64_t* key, const uint64_t* tag,
+                         const int64_t* ts, const uint32_t* instance, uint64_t n, uint64_t* clock,
+                         uint32_t n_instances, uint32_t flags, uint8_t* apply, uint32_t* applied,
+                         uint32_t* winner, uint32_t* counts);
 
 // ---- Object link batch (K7) ----------------------------------------------------
 size_t link_workspace_bytes(uint64_t n);

@@ -1916,6 +1916,59 @@ int sdgpu_indexer_diff(sdgpu_ctx* c, const uint64_t* w_key, const uint8_t* w_fla
   return 0;
 }
 
+// Sync ingest (sync.hip; the handle and the runs are shard.cpp's).  The checks
+// both variants share: nothing of the handle is read before they pass.
+static bool ingest_args_ok(const sdgpu_oplog* x, const uint64_t* key, const uint64_t* tag,
+                           const int64_t* ts, const uint32_t* instance, uint64_t n,
+                           const uint64_t* clock, uint32_t flags, const uint8_t* apply,
+                           const uint32_t* applied, const uint32_t* winner,
+                           const uint32_t* counts) {
+  if (!x || n >= (1ull << 31) || (flags & ~SDGPU_INGEST_NO_COMMIT)) return false;
+  if ((instance == nullptr) != (clock == nullptr)) return false;
+  return n == 0 || (key && tag && ts && apply && applied && winner && counts);
+}
+
+int sdgpu_oplog_add_device(sdgpu_oplog* x, const uint64_t* d_key, const uint64_t* d_tag,
+                           const int64_t* d_ts, uint64_t n, uint32_t* d_collisions, void* stream) {
+  if (!x || n >= (1ull << 31) || (n && (!d_key || !d_tag || !d_ts))) return -EINVAL;
+  if (n == 0 && !d_collisions) return 0;
+  return oplog_add_run(x, d_key, d_tag, d_ts, n, d_collisions, stream);
+}
+
+int sdgpu_oplog_latest_device(sdgpu_oplog* x, const uint64_t* d_key, uint64_t n, int64_t* d_ts,
+                              uint8_t* d_found, void* stream) {
+  if (!x || n >= (1ull << 31) || (n && (!d_key || !d_ts || !d_found))) return -EINVAL;
+  if (n == 0) return 0;
+  return oplog_latest_run(x, d_key, n, d_ts, d_found, stream);
+}
+
+int sdgpu_sync_ingest_device(sdgpu_oplog* x, const uint64_t* d_key, const uint64_t* d_tag,
+                             const int64_t* d_ts, const uint32_t* d_instance, uint64_t n,
+                             uint64_t* d_clock, uint32_t n_instances, uint32_t flags,
+                             uint8_t* d_apply, uint32_t* d_applied, uint32_t* d_winner,
+                             uint32_t* d_counts, void* stream) {
+  if (!ingest_args_ok(x, d_key, d_tag, d_ts, d_instance, n, d_clock, flags, d_apply, d_applied,
+                      d_winner, d_counts))
+    return -EINVAL;
+  if (n == 0 && !d_counts) return 0;
+  return sync_ingest_run(x, d_key, d_tag, d_ts, d_instance, n, d_clock, n_instances, flags,
+                         d_apply, d_applied, d_winner, d_counts, stream);
+}
+
+int sdgpu_sync_ingest(sdgpu_oplog* x, const uint64_t* key, const uint64_t* tag, const int64_t* ts,
+                      const uint32_t* instance, uint64_t n, uint64_t* clock, uint32_t n_instances,
+                      uint32_t flags, uint8_t* apply, uint32_t* applied, uint32_t* winner,
+                      uint32_t* counts) {
+  if (!ingest_args_ok(x, key, tag, ts, instance, n, clock, flags, apply, applied, winner, counts))
+    return -EINVAL;
+  if (n == 0) {  // no op: decided on the host
+    if (counts) memset(counts, 0, 4 * 4);
+    return 0;
+  }
+  return sync_ingest_host_run(x, key, tag, ts, instance, n, clock, n_instances, flags, apply,
+                              applied, winner, counts);
+}
+
 // Explorer search page (search.hip).  The columns a query reads; the checks
 // both variants share.
 struct SearchNeed {

@@ -179,6 +179,13 @@ struct sdgpu_index {
   uint64_t ub = 0;  // host upper bound of the slots in use
 };
 
+struct sdgpu_oplog {
+  sdgpu_ctx* ctx = nullptr;
+  DevBuf buf;       // [slots (cap + 1) * 32 | count 8 | pad 24]
+  OplogRef ref;
+  uint64_t ub = 0;  // host upper bound of the keys stored
+};
+
 namespace {
 
 // SDGPU_RETURN_AUTO: the compact return leg saves 2.4 B per returned row on
@@ -288,13 +295,25 @@ int stream_wait(sdgpu_comm* m, hipStream_t s, Clock::time_point deadline) {
 
 // ---- Object index ------------------------------------------------------------
 
-int index_alloc(sdgpu_ctx* c, DevBuf& b, uint64_t cap, IndexRef& r) {
-  const size_t bytes = 16 * cap + 32;
+// A table that lives as long as its handle (the Object index, the op log):
+// allocated here, and under poison_ws() filled here.
+int table_alloc(DevBuf& b, size_t bytes, const char* what) {
   void* p = nullptr;
   SD_TRY(hipMalloc(&p, bytes));
+  int rc = 0;
+  if (sdgpu::poison_ws()) rc = sdgpu::poison_dev(p, bytes, what);
+  if (rc != 0) {  // the caller gets no buffer to free
+    (void)hipFree(p);
+    return rc;
+  }
   b.p = p;
   b.cap = bytes;
-  if (sdgpu::poison_ws()) SD_TRY_RC(sdgpu::poison_dev(p, bytes, "index_table"));
+  return 0;
+}
+
+int index_alloc(sdgpu_ctx* c, DevBuf& b, uint64_t cap, IndexRef& r) {
+  SD_TRY_RC(table_alloc(b, 16 * cap + 32, "index_table"));
+  void* p = b.p;
   r.slots = static_cast<uint4*>(p);
   r.cap = cap;
   r.count = reinterpret_cast<unsigned long long*>(static_cast<uint8_t*>(p) + 16 * cap);
@@ -336,6 +355,44 @@ int index_reserve(sdgpu_index* x, uint64_t add, hipStream_t s) {
     x->buf = nb;
     x->ref = nr;
     used = live;
+  }
+  x->ub = used + add;
+  return 0;
+}
+
+// ---- op log (sync.hip) ---------------------------------------------------------
+
+constexpr uint64_t kOplogMaxCap = 1ull << 31;  // a slot number, the key ~0's included, is a u32
+
+int oplog_alloc(DevBuf& b, uint64_t cap, OplogRef& r) {
+  SD_TRY_RC(table_alloc(b, 32 * (cap + 1) + 32, "oplog_table"));
+  r.slots = static_cast<uint64_t*>(b.p);
+  r.cap = cap;
+  r.count = reinterpret_cast<unsigned long long*>(static_cast<uint8_t*>(b.p) + 32 * (cap + 1));
+  return 0;
+}
+
+// Make room for `add` more keys at load <= 1/2, as index_reserve does: the
+// stored count is read (one synchronisation of s) only when the host-side
+// upper bound says it may not fit; growth rehashes keys, timestamps and tags.
+int oplog_reserve(sdgpu_oplog* x, uint64_t add, hipStream_t s) {
+  if (x->ub + add <= x->ref.cap / 2) {
+    x->ub += add;
+    return 0;
+  }
+  unsigned long long used = 0;
+  SD_TRY(hipMemcpyAsync(&used, x->ref.count, 8, hipMemcpyDeviceToHost, s));
+  SD_TRY(hipStreamSynchronize(s));
+  if (used + add > x->ref.cap / 2) {
+    if (2 * (used + add) > kOplogMaxCap) return -ENOSPC;
+    DevBuf nb;
+    OplogRef nr;
+    SD_TRY_RC(oplog_alloc(nb, std::min(pow2_at_least(4 * (used + add)), kOplogMaxCap), nr));
+    SD_TRY(oplog_rehash_launch(x->ref, nr, s));
+    SD_TRY(hipStreamSynchronize(s));
+    (void)hipFree(x->buf.p);
+    x->buf = nb;
+    x->ref = nr;
   }
   x->ub = used + add;
   return 0;
@@ -1469,6 +1526,167 @@ int sdgpu_index_stats(sdgpu_index* x, uint64_t out[3]) {
   SD_TRY(hipSetDevice(x->ctx->device));
   return index_read_stats(x, pick(x->ctx, nullptr), out);
 }
+
+// ---- op log ----------------------------------------------------------------------------
+
+int sdgpu_oplog_create(sdgpu_ctx* c, uint64_t capacity_hint, sdgpu_oplog** out) {
+  if (!c || !out) return -EINVAL;
+  *out = nullptr;
+  if (capacity_hint > kOplogMaxCap / 2) return -EINVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  SD_TRY(hipSetDevice(c->device));
+  sdgpu_oplog* x = new (std::nothrow) sdgpu_oplog;
+  if (!x) return -ENOMEM;
+  x->ctx = c;
+  int rc = oplog_alloc(x->buf, pow2_at_least(2 * std::max<uint64_t>(capacity_hint, 1)), x->ref);
+  if (rc == 0 && oplog_clear_launch(x->ref, c->stream) != hipSuccess) rc = -EIO;
+  if (rc == 0 && hipStreamSynchronize(c->stream) != hipSuccess) rc = -EIO;
+  if (rc) {
+    if (x->buf.p) (void)hipFree(x->buf.p);
+    delete x;
+    return rc;
+  }
+  *out = x;
+  return 0;
+}
+
+int sdgpu_oplog_destroy(sdgpu_oplog* x) {
+  if (!x) return -EINVAL;
+  {
+    std::lock_guard<std::mutex> g(x->ctx->mu);
+    (void)hipSetDevice(x->ctx->device);
+    (void)hipStreamSynchronize(x->ctx->stream);
+    if (x->ctx->last) (void)hipStreamSynchronize(x->ctx->last);
+    if (x->buf.p) (void)hipFree(x->buf.p);
+  }
+  delete x;
+  return 0;
+}
+
+int sdgpu_oplog_clear(sdgpu_oplog* x, void* stream) {
+  if (!x) return -EINVAL;
+  std::lock_guard<std::mutex> g(x->ctx->mu);
+  SD_TRY(hipSetDevice(x->ctx->device));
+  SD_TRY(oplog_clear_launch(x->ref, pick(x->ctx, stream)));
+  x->ub = 0;
+  return 0;
+}
+
+int sdgpu_oplog_stats(sdgpu_oplog* x, uint64_t out[2]) {
+  if (!x || !out) return -EINVAL;
+  std::lock_guard<std::mutex> g(x->ctx->mu);
+  SD_TRY(hipSetDevice(x->ctx->device));
+  hipStream_t s = pick(x->ctx, nullptr);
+  unsigned long long used = 0, special = 0;
+  SD_TRY(hipMemcpyAsync(&used, x->ref.count, 8, hipMemcpyDeviceToHost, s));
+  SD_TRY(hipMemcpyAsync(&special, x->ref.slots + 4 * x->ref.cap, 8, hipMemcpyDeviceToHost, s));
+  SD_TRY(hipStreamSynchronize(s));
+  out[0] = used + (special == 0 ? 1 : 0);  // the key ~0's slot: key word 0 once entered
+  out[1] = x->ref.cap;
+  return 0;
+}
+
+}  // extern "C"
+
+namespace sdgpu {
+
+int oplog_add_run(sdgpu_oplog* x, const uint64_t* d_key, const uint64_t* d_tag,
+                  const int64_t* d_ts, uint64_t n, uint32_t* d_collisions, void* stream) {
+  sdgpu_ctx* c = x->ctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  SD_TRY(hipSetDevice(c->device));
+  hipStream_t s = pick(c, stream);
+  if (n) {
+    SD_TRY_RC(oplog_reserve(x, n, s));
+    SD_TRY_RC(ensure_dev(c, c->link_ws, oplog_add_workspace_bytes(n, d_collisions != nullptr)));
+  }
+  SD_TRY(oplog_add_launch(x->ref, d_key, d_tag, d_ts, n, d_collisions, c->link_ws.p, s, c->kt()));
+  return 0;
+}
+
+int oplog_latest_run(sdgpu_oplog* x, const uint64_t* d_key, uint64_t n, int64_t* d_ts,
+                     uint8_t* d_found, void* stream) {
+  std::lock_guard<std::mutex> g(x->ctx->mu);
+  SD_TRY(hipSetDevice(x->ctx->device));
+  hipStream_t s = pick(x->ctx, stream);
+  SD_TRY(oplog_latest_launch(x->ref, d_key, n, d_ts, d_found, s, x->ctx->kt()));
+  return 0;
+}
+
+int sync_ingest_run(sdgpu_oplog* x, const uint64_t* d_key, const uint64_t* d_tag,
+                    const int64_t* d_ts, const uint32_t* d_instance, uint64_t n, uint64_t* d_clock,
+                    uint32_t n_instances, uint32_t flags, uint8_t* d_apply, uint32_t* d_applied,
+                    uint32_t* d_winner, uint32_t* d_counts, void* stream) {
+  sdgpu_ctx* c = x->ctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  SD_TRY(hipSetDevice(c->device));
+  hipStream_t s = pick(c, stream);
+  if (n) {
+    SD_TRY_RC(oplog_reserve(x, n, s));
+    SD_TRY_RC(ensure_dev(c, c->link_ws, sync_ingest_workspace_bytes(n)));
+  }
+  SD_TRY(sync_ingest_launch(x->ref, d_key, d_tag, d_ts, d_instance, n, d_clock, n_instances,
+                            !(flags & SDGPU_INGEST_NO_COMMIT), d_apply, d_applied, d_winner,
+                            d_counts, c->link_ws.p, s, c->kt()));
+  return 0;
+}
+
+int sync_ingest_host_run(sdgpu_oplog* x, const uint64_t* key, const uint64_t* tag,
+                         const int64_t* ts, const uint32_t* instance, uint64_t n, uint64_t* clock,
+                         uint32_t n_instances, uint32_t flags, uint8_t* apply, uint32_t* applied,
+                         uint32_t* winner, uint32_t* counts) {
+  sdgpu_ctx* c = x->ctx;
+  std::lock_guard<std::mutex> g(c->mu);
+  SD_TRY(hipSetDevice(c->device));
+  hipStream_t s = pick(c, nullptr);
+  SD_TRY_RC(oplog_reserve(x, n, s));
+  // workspace | key, tag, ts, instance, clock | apply, applied, winner, counts
+  // in the context's link workspace (as sdgpu_indexer_diff lays it out).  The
+  // caller's arrays are pageable: every copy below is staged by the runtime,
+  // and the two lists come back in copies of their own once their lengths are
+  // known -- nine copy commands around the launches, which a 1000-op page pays
+  // in full
+  size_t o = align_up(sync_ingest_workspace_bytes(n), 256);
+  auto take = [&](size_t bytes) {
+    const size_t at = o;
+    o += align_up(bytes, 256);
+    return at;
+  };
+  const size_t o_k = take(8 * n), o_t = take(8 * n), o_ts = take(8 * n);
+  const size_t o_in = take(instance ? 4 * n : 0), o_cl = take(8ull * n_instances);
+  const size_t o_ap = take(n), o_al = take(4 * n), o_wl = take(4 * n), o_cn = take(4 * 4);
+  SD_TRY_RC(ensure_dev(c, c->link_ws, o));
+  uint8_t* base = static_cast<uint8_t*>(c->link_ws.p);
+  auto u64p = [&](size_t at) { return reinterpret_cast<uint64_t*>(base + at); };
+  auto u32p = [&](size_t at) { return reinterpret_cast<uint32_t*>(base + at); };
+  SD_TRY(hipMemcpyAsync(base + o_k, key, 8 * n, hipMemcpyHostToDevice, s));
+  SD_TRY(hipMemcpyAsync(base + o_t, tag, 8 * n, hipMemcpyHostToDevice, s));
+  SD_TRY(hipMemcpyAsync(base + o_ts, ts, 8 * n, hipMemcpyHostToDevice, s));
+  if (instance) SD_TRY(hipMemcpyAsync(base + o_in, instance, 4 * n, hipMemcpyHostToDevice, s));
+  if (instance && n_instances)
+    SD_TRY(hipMemcpyAsync(base + o_cl, clock, 8ull * n_instances, hipMemcpyHostToDevice, s));
+  SD_TRY(sync_ingest_launch(x->ref, u64p(o_k), u64p(o_t), reinterpret_cast<int64_t*>(base + o_ts),
+                            instance ? u32p(o_in) : nullptr, n, instance ? u64p(o_cl) : nullptr,
+                            n_instances, !(flags & SDGPU_INGEST_NO_COMMIT), base + o_ap,
+                            u32p(o_al), u32p(o_wl), u32p(o_cn), base, s, c->kt()));
+  SD_TRY(hipMemcpyAsync(counts, base + o_cn, 4 * 4, hipMemcpyDeviceToHost, s));
+  SD_TRY(hipMemcpyAsync(apply, base + o_ap, n, hipMemcpyDeviceToHost, s));
+  if (instance && n_instances)
+    SD_TRY(hipMemcpyAsync(clock, base + o_cl, 8ull * n_instances, hipMemcpyDeviceToHost, s));
+  SD_TRY(hipStreamSynchronize(s));
+  // only the listed ops travel back
+  if (counts[0])
+    SD_TRY(hipMemcpy(applied, base + o_al, 4 * static_cast<size_t>(counts[0]),
+                     hipMemcpyDeviceToHost));
+  if (counts[1])
+    SD_TRY(hipMemcpy(winner, base + o_wl, 4 * static_cast<size_t>(counts[1]),
+                     hipMemcpyDeviceToHost));
+  return 0;
+}
+
+}  // namespace sdgpu
+
+extern "C" {
 
 int sdgpu_index_lookup_device(sdgpu_index* x, const uint64_t* d_key, uint64_t n, uint32_t* d_value,
                               void* stream) {
