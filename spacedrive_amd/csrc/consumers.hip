@@ -5,15 +5,15 @@
 // found 512 at a time and deleted.  Here: one pass marks every Object id that
 // some file_path references (a byte per id, plain stores: marking is
 // idempotent, so no atomics are needed), a second pass keeps
-// the unreferenced ids of the Object list, in list order (4096-id tiles:
-// count, one scan of the tile counts, in-tile ballot ranks), ready for the
-// caller's delete batches.
+// the unreferenced ids of the Object list, in list order (the shared tile
+// compaction of compact_device.hpp), ready for the caller's delete batches.
 //
 // Thumbnail shards (/root/reference/core/src/object/media/thumbnail/shard.rs:4-8):
 // a thumbnail lives in directory cas_id[0..2], the first digest byte, i.e. the
 // low byte of the little-endian cas key.  Here: a batch's rows counting-sorted
 // by that byte (256 directories), so a thumbnailer writes each directory's
 // files together; counts per directory alongside.
+#include "compact_device.hpp"
 #include "internal.hpp"
 #include "scan_device.hpp"
 
@@ -21,12 +21,10 @@ namespace sdgpu {
 
 namespace {
 
-constexpr int kThreads = 256;
-
-uint32_t grid_for(uint64_t n, uint64_t per = kThreads) {
-  const uint64_t g = (n + per - 1) / per;
-  return static_cast<uint32_t>(g == 0 ? 1 : (g < 65535 ? g : 65535));
-}
+using compact::kRows;
+using compact::kThreads;
+using compact::kTile;
+using compact::kWaves;
 
 // mark[o] = 1: some file_path references Object o (negative = NULL object_id).
 // Workgroups go to the 8 XCDs round-robin (block b on XCD b % 8), so block b
@@ -73,25 +71,24 @@ __device__ __forceinline__ uint8_t mark_of(int32_t o, const uint8_t* mark, uint3
   return mark[c];
 }
 
-// The Object list in tiles of kORows x kThreads ids: id tile + k * kThreads + t
-// (coalesced), and (k, t) order is list order, so in-tile ranks from
-// per-(k, wave) ballots keep the orphans in list order.
-constexpr int kORows = 16;
-constexpr uint64_t kOTile = static_cast<uint64_t>(kORows) * kThreads;
-constexpr int kOWaves = kThreads / 64;
-
-// the kORows ids of a thread (loads unconditional, tail masked after), then
-// their mark bytes
-__device__ __forceinline__ void obj_tile(const int32_t* __restrict__ obj, uint64_t n, uint64_t tile,
-                                         const uint8_t* __restrict__ bits, uint32_t max_id,
-                                         int32_t (&o)[kORows], uint8_t (&m)[kORows]) {
+// The Object list in the compaction's tiles (compact_device.hpp): the kRows ids
+// of a thread (loads unconditional, tail masked after), then their mark bytes;
+// bit k of the result: the k-th of them is an orphan.
+__device__ __forceinline__ uint32_t obj_tile(const int32_t* __restrict__ obj, uint64_t n, uint64_t tile,
+                                             const uint8_t* __restrict__ bits, uint32_t max_id,
+                                             int32_t (&o)[kRows]) {
+  uint8_t m[kRows];
 #pragma unroll
-  for (int k = 0; k < kORows; ++k) o[k] = obj[min(tile + k * kThreads + threadIdx.x, n - 1)];
+  for (int k = 0; k < kRows; ++k) o[k] = obj[min(tile + k * kThreads + threadIdx.x, n - 1)];
 #pragma unroll
-  for (int k = 0; k < kORows; ++k)
+  for (int k = 0; k < kRows; ++k)
     if (tile + k * kThreads + threadIdx.x >= n) o[k] = -1;
 #pragma unroll
-  for (int k = 0; k < kORows; ++k) m[k] = mark_of(o[k], bits, max_id);
+  for (int k = 0; k < kRows; ++k) m[k] = mark_of(o[k], bits, max_id);
+  uint32_t f = 0;
+#pragma unroll
+  for (int k = 0; k < kRows; ++k) f |= (orphan(o[k], m[k], max_id) ? 1u : 0u) << k;
+  return f;
 }
 
 // orphans per tile
@@ -100,23 +97,10 @@ __global__ __launch_bounds__(kThreads) void k_orphan_count(const int32_t* __rest
                                                            const uint8_t* __restrict__ bits,
                                                            uint32_t max_id,
                                                            uint32_t* __restrict__ cnt) {
-  __shared__ uint32_t sw[kOWaves];
-  const uint64_t tile = static_cast<uint64_t>(blockIdx.x) * kOTile;
-  int32_t o[kORows];
-  uint8_t m[kORows];
-  obj_tile(obj, n, tile, bits, max_id, o, m);
-  uint32_t c = 0;
-#pragma unroll
-  for (int k = 0; k < kORows; ++k) c += orphan(o[k], m[k], max_id) ? 1u : 0u;
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
-  if (__lane_id() == 0) sw[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-    for (int w = 0; w < kOWaves; ++w) t += sw[w];
-    cnt[blockIdx.x] = t;
-  }
+  const uint64_t tile = static_cast<uint64_t>(blockIdx.x) * kTile;
+  int32_t o[kRows];
+  const uint32_t t = compact::tile_count(obj_tile(obj, n, tile, bits, max_id, o));
+  if (threadIdx.x == 0) cnt[blockIdx.x] = t;
 }
 
 // stable compaction: tile b writes its orphans from the scanned offset, in order
@@ -126,38 +110,15 @@ __global__ __launch_bounds__(kThreads) void k_orphan_write(const int32_t* __rest
                                                            uint32_t max_id,
                                                            const uint32_t* __restrict__ offs,
                                                            int32_t* __restrict__ out) {
-  __shared__ uint32_t off[kORows][kOWaves];
-  const uint64_t tile = static_cast<uint64_t>(blockIdx.x) * kOTile;
-  const uint32_t lane = __lane_id(), w = threadIdx.x >> 6;
-  const uint64_t lt = (1ull << lane) - 1ull;
-  int32_t o[kORows];
-  uint8_t m[kORows];
-  uint32_t pre[kORows], f = 0;
-  obj_tile(obj, n, tile, bits, max_id, o, m);
+  __shared__ uint32_t off[kRows][kWaves];
+  const uint64_t tile = static_cast<uint64_t>(blockIdx.x) * kTile;
+  int32_t o[kRows];
+  uint32_t pre[kRows];
+  const uint32_t f = obj_tile(obj, n, tile, bits, max_id, o);
+  compact::tile_offsets(f, [&] { return offs[blockIdx.x]; }, off, pre);
+  const uint32_t w = threadIdx.x >> 6;
 #pragma unroll
-  for (int k = 0; k < kORows; ++k) {
-    const bool is = orphan(o[k], m[k], max_id);
-    f |= (is ? 1u : 0u) << k;
-    const uint64_t b = __ballot(is);
-    pre[k] = __popcll(b & lt);
-    if (lane == 0) off[k][w] = __popcll(b);
-  }
-  __syncthreads();
-  static_assert(kORows * kOWaves == 64, "one wave scans the (row step, wave) counts");
-  if (threadIdx.x < 64) {  // (k, wave) order -- k-major, the array's order -- is list order
-    uint32_t* f = &off[0][0];
-    const uint32_t a = f[lane];
-    uint32_t inc = a;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t x = __shfl_up(inc, d);
-      if (lane >= static_cast<uint32_t>(d)) inc += x;
-    }
-    f[lane] = offs[blockIdx.x] + inc - a;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < kORows; ++k)
+  for (int k = 0; k < kRows; ++k)
     if (f >> k & 1u) out[off[k][w] + pre[k]] = o[k];
 }
 
@@ -197,7 +158,6 @@ __global__ __launch_bounds__(kThreads) void k_thumb_scatter(const uint8_t* __res
                                                             uint64_t n,
                                                             const uint32_t* __restrict__ offs,
                                                             uint32_t* __restrict__ order) {
-  constexpr uint32_t kWaves = kThreads / 64;
   __shared__ uint32_t cur[kShardBins];
   __shared__ uint32_t wcnt[kWaves][kShardBins];
   static_assert(kShardBins == kThreads, "one cursor per thread");
@@ -245,7 +205,7 @@ __global__ void k_thumb_counts(const uint32_t* __restrict__ offs, uint32_t* __re
 
 size_t orphan_workspace_bytes(uint64_t n_obj, uint32_t max_id) {
   const uint64_t map = (static_cast<uint64_t>(max_id) + 1 + 255) / 256 * 256;
-  const uint64_t blocks = (n_obj + kOTile - 1) / kOTile;
+  const uint64_t blocks = compact::tiles_for(n_obj);
   return map + 4 * (blocks + 1) + 4 * (scan::tiles_for(blocks) + 1) + 1024;
 }
 
@@ -253,7 +213,7 @@ hipError_t orphan_objects_launch(const int32_t* obj, uint64_t n_obj, const int32
                                  uint64_t n_fp, uint32_t max_id, int32_t* out, uint32_t* d_count,
                                  void* ws, hipStream_t s) {
   const uint64_t map = (static_cast<uint64_t>(max_id) + 1 + 255) / 256 * 256;
-  const uint64_t blocks = (n_obj + kOTile - 1) / kOTile;
+  const uint64_t blocks = compact::tiles_for(n_obj);
   uint8_t* bits = static_cast<uint8_t*>(ws);
   uint32_t* cnt = reinterpret_cast<uint32_t*>(bits + map);
   uint32_t* tiles = cnt + blocks + 1;

@@ -4,6 +4,7 @@
 // and the return of the reps to their rows (full gather or compact pairs).
 // Digits come from h = mix64(key) as in the grouping (dedup.hip): the shard
 // is h's top kShardBits bits.
+#include "compact_device.hpp"
 #include "internal.hpp"
 #include "part_device.hpp"
 #include "scan_device.hpp"
@@ -324,10 +325,12 @@ __global__ void k_recv_summary(const uint3* __restrict__ rrec, uint32_t world, u
 // its (source -> owner) message, rep} -- 8 B per linked row instead of 4 B
 // per row.  Tiles of kRetTile received rows never straddle a source's
 // segment (the host lays them out per segment, RetTiles), so the pairs come
-// out grouped by source in row order: tile counts, one scan, ranked writes.
-constexpr int kRetThreads = 256;
-constexpr int kRetRows = 16;
-constexpr uint32_t kRetTile = kRetThreads * kRetRows;
+// out grouped by source in row order: the shared tile compaction
+// (compact_device.hpp) per segment.
+constexpr int kRetThreads = compact::kThreads;
+constexpr int kRetRows = compact::kRows;
+constexpr uint32_t kRetTile = compact::kTile;
+static_assert(kRetTile == kRetTileRows, "the host lays the tiles out");
 
 __device__ __forceinline__ uint32_t ret_segment(const RetTiles& st, uint32_t blk) {
   uint32_t p = 0;
@@ -338,23 +341,19 @@ __device__ __forceinline__ uint32_t ret_segment(const RetTiles& st, uint32_t blk
 __global__ __launch_bounds__(kRetThreads) void k_ret_count(RetTiles st, const uint3* __restrict__ rrec,
                                                            const uint32_t* __restrict__ rrep,
                                                            uint32_t* __restrict__ cnt) {
-  __shared__ uint32_t sc[kRetThreads / 64];
   const uint32_t blk = blockIdx.x;
-  uint32_t c = 0;
+  uint32_t f = 0;
   if (blk < st.tstart[st.world]) {
     const uint32_t p = ret_segment(st, blk);
     const uint32_t k0 = st.roff[p] + (blk - st.tstart[p]) * kRetTile, k1 = st.roff[p + 1];
 #pragma unroll
     for (int u = 0; u < kRetRows; ++u) {
       const uint32_t k = k0 + u * kRetThreads + threadIdx.x;
-      if (k < k1) c += rrep[k] != rrec[k].z;
+      if (k < k1) f |= (rrep[k] != rrec[k].z ? 1u : 0u) << u;
     }
   }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
-  if (__lane_id() == 0) sc[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) cnt[blk] = sc[0] + sc[1] + sc[2] + sc[3];
+  const uint32_t c = compact::tile_count(f);
+  if (threadIdx.x == 0) cnt[blk] = c;
 }
 
 // cnt: exclusive scan of the tile counts (cnt[tiles] = total).  retcnt[p] =
@@ -364,45 +363,28 @@ __global__ __launch_bounds__(kRetThreads) void k_ret_write(RetTiles st, const ui
                                                            const uint32_t* __restrict__ cnt,
                                                            uint2* __restrict__ ret,
                                                            int64_t* __restrict__ retcnt) {
-  __shared__ uint32_t oc[kRetRows][kRetThreads / 64];
-  const uint32_t blk = blockIdx.x, lane = __lane_id(), w = threadIdx.x >> 6;
+  __shared__ uint32_t oc[kRetRows][compact::kWaves];
+  const uint32_t blk = blockIdx.x, w = threadIdx.x >> 6;
   if (blk == 0 && threadIdx.x < st.world)
     retcnt[threadIdx.x] = static_cast<int64_t>(cnt[st.tstart[threadIdx.x + 1]]) -
                           static_cast<int64_t>(cnt[st.tstart[threadIdx.x]]);
   if (blk >= st.tstart[st.world]) return;  // the one block of an empty receive
   const uint32_t p = ret_segment(st, blk);
   const uint32_t k0 = st.roff[p] + (blk - st.tstart[p]) * kRetTile, k1 = st.roff[p + 1];
-  const uint64_t lt = (1ull << lane) - 1ull;
-  bool f[kRetRows];
-  uint32_t v[kRetRows], pr[kRetRows];
+  uint32_t f = 0, v[kRetRows], pr[kRetRows];
 #pragma unroll
   for (int u = 0; u < kRetRows; ++u) {
     const uint32_t k = k0 + u * kRetThreads + threadIdx.x;
     const uint32_t kk = k < k1 ? k : k1 - 1;
     v[u] = rrep[kk];
-    f[u] = k < k1 && v[u] != rrec[kk].z;
-    const uint64_t b = __ballot(f[u]);
-    pr[u] = __popcll(b & lt);
-    if (lane == 0) oc[u][w] = __popcll(b);
+    f |= (k < k1 && v[u] != rrec[kk].z ? 1u : 0u) << u;
   }
-  __syncthreads();
-  static_assert(kRetRows * (kRetThreads / 64) == 64, "one wave scans the (row step, wave) counts");
-  if (threadIdx.x < 64) {
-    uint32_t* e = &oc[0][0];
-    const uint32_t a = e[lane];
-    uint32_t inc = a;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t o = __shfl_up(inc, d);
-      if (lane >= static_cast<uint32_t>(d)) inc += o;
-    }
-    e[lane] = cnt[blk] - cnt[st.tstart[p]] + inc - a;  // index inside the segment's pairs
-  }
-  __syncthreads();
+  // index inside the segment's pairs
+  compact::tile_offsets(f, [&] { return cnt[blk] - cnt[st.tstart[p]]; }, oc, pr);
   const uint32_t seg0 = cnt[st.tstart[p]];
 #pragma unroll
   for (int u = 0; u < kRetRows; ++u)
-    if (f[u]) {
+    if (f >> u & 1u) {
       const uint32_t k = k0 + u * kRetThreads + threadIdx.x;
       ret[seg0 + oc[u][w] + pr[u]] = make_uint2(k - st.roff[p], v[u]);
     }

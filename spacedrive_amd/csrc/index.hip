@@ -407,27 +407,26 @@ __global__ __launch_bounds__(kThreads) void k_index_export(IndexRef t, uint64_t*
   }
 }
 
-uint32_t grid_for(uint64_t n) {
-  const uint64_t g = (n + kThreads - 1) / kThreads;
-  return static_cast<uint32_t>(g == 0 ? 1 : (g < 8192 ? g : 8192));
-}
+constexpr uint32_t kMaxGrid = 8192;
 
 }  // namespace
 
 hipError_t index_clear_launch(const IndexRef& t, hipStream_t s) {
-  k_index_clear<<<grid_for(t.cap), kThreads, 0, s>>>(t);
+  k_index_clear<<<grid_for(t.cap, kThreads, kMaxGrid), kThreads, 0, s>>>(t);
   return hipGetLastError();
 }
 
 hipError_t index_rehash_launch(const IndexRef& from, const IndexRef& to, hipStream_t s) {
-  k_index_clear<<<grid_for(to.cap), kThreads, 0, s>>>(to);
-  k_index_rehash<<<grid_for(from.cap), kThreads, 0, s>>>(from, to);
+  k_index_clear<<<grid_for(to.cap, kThreads, kMaxGrid), kThreads, 0, s>>>(to);
+  k_index_rehash<<<grid_for(from.cap, kThreads, kMaxGrid), kThreads, 0, s>>>(from, to);
   return hipGetLastError();
 }
 
 hipError_t index_objects_launch(const IndexRef& t, const uint64_t* key, const uint32_t* handle,
                                 uint64_t n, uint32_t world, uint32_t rank, hipStream_t s) {
-  if (n) k_index_objects<<<grid_for(n), kThreads, 0, s>>>(t, key, handle, n, world, rank);
+  if (n)
+    k_index_objects<<<grid_for(n, kThreads, kMaxGrid), kThreads, 0, s>>>(t, key, handle, n, world,
+                                                                          rank);
   return hipGetLastError();
 }
 
@@ -436,11 +435,11 @@ hipError_t index_probe_launch(const IndexRef& t, const GroupInput& in, uint32_t 
   if (in.n == 0) return hipSuccess;
   KScope k(timer, "index_probe", s);
   if (in.rec12)
-    k_index_probe<<<grid_for(in.n), kThreads, 0, s>>>(
+    k_index_probe<<<grid_for(in.n, kThreads, kMaxGrid), kThreads, 0, s>>>(
         t, RecIn{reinterpret_cast<const uint3*>(in.rec12), in.valid}, in.n, chunk_rows, rep,
         valid_out);
   else
-    k_index_probe<<<grid_for(in.n), kThreads, 0, s>>>(
+    k_index_probe<<<grid_for(in.n, kThreads, kMaxGrid), kThreads, 0, s>>>(
         t, RowsIn{in.key, in.valid, in.rank, in.rank_base}, in.n, chunk_rows, rep, valid_out);
   return hipGetLastError();
 }
@@ -451,10 +450,10 @@ hipError_t index_creators_launch(const IndexRef& t, const GroupInput& in, const 
   if (in.n == 0) return hipSuccess;
   KScope k(timer, "index_insert", s);
   if (in.rec12)
-    k_index_creators<<<grid_for(in.n), kThreads, 0, s>>>(
+    k_index_creators<<<grid_for(in.n, kThreads, kMaxGrid), kThreads, 0, s>>>(
         t, RecIn{reinterpret_cast<const uint3*>(in.rec12), nullptr}, in.n, rep, grouped, skip);
   else
-    k_index_creators<<<grid_for(in.n), kThreads, 0, s>>>(
+    k_index_creators<<<grid_for(in.n, kThreads, kMaxGrid), kThreads, 0, s>>>(
         t, RowsIn{in.key, nullptr, in.rank, in.rank_base}, in.n, rep, grouped, skip);
   return hipGetLastError();
 }
@@ -463,7 +462,7 @@ hipError_t index_lookup_launch(const IndexRef& t, const uint64_t* key, uint64_t 
                                uint32_t* value, hipStream_t s, KTimer* timer) {
   if (n == 0) return hipSuccess;
   KScope k(timer, "index_lookup", s);
-  k_index_lookup<<<grid_for(n), kThreads, 0, s>>>(t, key, n, value);
+  k_index_lookup<<<grid_for(n, kThreads, kMaxGrid), kThreads, 0, s>>>(t, key, n, value);
   return hipGetLastError();
 }
 
@@ -475,7 +474,7 @@ hipError_t index_remove_launch(const IndexRef& t, const uint64_t* key, const uin
   }
   if (n == 0) return hipSuccess;
   KScope k(timer, "index_remove", s);
-  k_index_remove<<<grid_for(n), kThreads, 0, s>>>(t, key, value, n, removed);
+  k_index_remove<<<grid_for(n, kThreads, kMaxGrid), kThreads, 0, s>>>(t, key, value, n, removed);
   return hipGetLastError();
 }
 
@@ -496,8 +495,9 @@ hipError_t index_remove_objects_launch(const IndexRef& t, const int32_t* handle,
   const hipError_t e = hipMemsetAsync(mark, 0, index_mark_workspace_bytes(max_handle), s);
   if (e != hipSuccess) return e;
   KScope k(timer, "index_remove_objects", s);
-  k_index_mark<<<grid_for(n), kThreads, 0, s>>>(handle, n, max_handle, mark);
-  k_index_remove_marked<<<grid_for(t.cap), kThreads, 0, s>>>(t, mark, max_handle, removed);
+  k_index_mark<<<grid_for(n, kThreads, kMaxGrid), kThreads, 0, s>>>(handle, n, max_handle, mark);
+  k_index_remove_marked<<<grid_for(t.cap, kThreads, kMaxGrid), kThreads, 0, s>>>(
+      t, mark, max_handle, removed);
   return hipGetLastError();
 }
 
@@ -506,8 +506,8 @@ hipError_t index_export_launch(const IndexRef& t, uint64_t* key, uint32_t* value
   const hipError_t e = hipMemsetAsync(d_count, 0, sizeof(uint32_t), s);
   if (e != hipSuccess) return e;
   KScope k(timer, "index_export", s);
-  k_index_export<<<grid_for(t.cap / kExportRows), kThreads, 0, s>>>(t, key, value, cap_out,
-                                                                    d_count);
+  k_index_export<<<grid_for(t.cap / kExportRows, kThreads, kMaxGrid), kThreads, 0, s>>>(
+      t, key, value, cap_out, d_count);
   return hipGetLastError();
 }
 

@@ -8,47 +8,38 @@
 // (:349-369); walk.rs:624-636 asks per walked directory which rows of that
 // directory were not found (`id NOT IN (...)`, indexer/mod.rs:338-388).
 //
-// Here: the rows' keys go into an open-addressing table in the context's
-// workspace (8-byte slots, capacity a power of two >= 2 x n_r, linear probing
-// from row_hash(key), empty slot ~0; the key ~0 owns the slot one past the
-// table, as thumbnail_remover.hip and index.hip do it); every slot keeps the
-// lowest row that holds its key (first_row, atomicMin) and every row the slot
-// it ended in (slot_of).  The walked directories go into a second, small set
-// table.  Then
+// Here: the rows' keys go into a key set in the context's workspace
+// (keyset_device.hpp: 8-byte slots, the key ~0 owns the slot one past the
+// table); every slot keeps the lowest row that holds its key (first_row,
+// atomicMin) and every row the slot it ended in (slot_of).  The walked
+// directories go into a second, small key set.  Then
 //   k_idx_probe  one lane per walked entry: match, state, and hit[slot] = 1 (a
 //                plain byte store, idempotent) for entries that were in their
 //                parent's listing;
 //   k_idx_rows   one lane per row: remove_flag = directory walked && !hit;
-//   k_idx_count / scan / k_idx_write: the three lists as ONE compaction -- the
-//                tiles of create, update and remove are laid behind one
-//                another, counted, scanned once, and every list's offsets and
-//                length are differences of that one scan.
+//   k_idx_count / scan / k_idx_write: the three lists as ONE compaction
+//                (compact_device.hpp) -- the tiles of create, update and
+//                remove are laid behind one another, counted, scanned once,
+//                and every list's offsets and length are differences of that
+//                one scan.
+#include "compact_device.hpp"
 #include "internal.hpp"
-#include "rows_device.hpp"
+#include "keyset_device.hpp"
 #include "scan_device.hpp"
 
 namespace sdgpu {
 
 namespace {
 
-constexpr uint64_t kEmptyKey = ~0ull;
+using compact::kRows;
+using compact::kThreads;
+using compact::kTile;
+using compact::kWaves;
 constexpr uint32_t kMiss = 0xFFFFFFFFu;
-constexpr int kThreads = 256;
-constexpr uint64_t kMinCap = 1024;
+constexpr uint32_t kMaxGrid = 2048;
 
 constexpr uint8_t kIsDir = 1, kAncestor = 2, kNoMetadata = 2;
 constexpr uint8_t kCreate = 0, kUnchanged = 1, kUpdate = 2, kKindChanged = 3;
-
-constexpr int kCRows = 16;  // compaction: positions per thread
-constexpr uint64_t kCTile = static_cast<uint64_t>(kCRows) * kThreads;
-constexpr int kCWaves = kThreads / 64;
-
-uint64_t table_cap(uint64_t n) {
-  uint64_t cap = kMinCap;
-  // 2^31 slots at the most: a slot number, the special one included, is a u32
-  while (cap < 2 * n && cap < (1ull << 31)) cap <<= 1;
-  return cap;
-}
 
 struct IdxWs {
   uint64_t cap, dcap;    // slots of the row table / the directory set
@@ -70,40 +61,28 @@ struct IdxWs {
 
 IdxWs idx_ws(uint64_t n_w, uint64_t n_wd, uint64_t n_r, void* ws) {
   IdxWs w;
-  w.cap = table_cap(n_r);
-  w.dcap = table_cap(n_wd);
-  w.bw = (n_w + kCTile - 1) / kCTile;
-  w.br = (n_r + kCTile - 1) / kCTile;
-  uint8_t* p = static_cast<uint8_t*>(ws);
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    uint8_t* q = p ? p + o : nullptr;
-    o += (bytes + 255) / 256 * 256;
-    return q;
-  };
-  w.table = reinterpret_cast<uint64_t*>(take(8 * w.cap));
-  w.dtable = reinterpret_cast<uint64_t*>(take(8 * w.dcap));
-  w.first_row = reinterpret_cast<uint32_t*>(take(4 * (w.cap + 1)));
-  w.fill_bytes = o;
-  w.hit = take(w.cap + 2);
-  w.slot_of = reinterpret_cast<uint32_t*>(take(4 * n_r));
-  w.remove_flag = take(n_r);
+  w.cap = keyset_cap(n_r);
+  w.dcap = keyset_cap(n_wd);
+  w.bw = compact::tiles_for(n_w);
+  w.br = compact::tiles_for(n_r);
+  Carve c(ws);
+  w.table = c.take<uint64_t>(w.cap);
+  w.dtable = c.take<uint64_t>(w.dcap);
+  w.first_row = c.take<uint32_t>(w.cap + 1);
+  w.fill_bytes = c.bytes();
+  w.hit = c.take(w.cap + 2);
+  w.slot_of = c.take<uint32_t>(n_r);
+  w.remove_flag = c.take(n_r);
   const uint64_t blocks = 2 * w.bw + w.br;
-  w.cnt = reinterpret_cast<uint32_t*>(take(4 * (blocks + 1)));
-  w.tiles = reinterpret_cast<uint32_t*>(take(4 * (static_cast<size_t>(scan::tiles_for(blocks)) + 1)));
-  w.bytes = o;
+  w.cnt = c.take<uint32_t>(blocks + 1);
+  w.tiles = c.take<uint32_t>(static_cast<size_t>(scan::tiles_for(blocks)) + 1);
+  w.bytes = c.bytes();
   return w;
 }
 
-uint32_t grid_for(uint64_t n, uint64_t per) {
-  const uint64_t g = (n + per - 1) / per;
-  return static_cast<uint32_t>(g == 0 ? 1 : (g < 2048 ? g : 2048));
-}
-
-// Items [0, n_r): slot_of[j] = the slot r_key[j] ends in -- the first thread to
-// claim an empty slot (64-bit CAS) places the key, every other copy of it
-// finds it -- and first_row[slot] = min(j).  Items [n_r, n_r + n_wd): the
-// walked directories' keys into their set table.
+// Items [0, n_r): slot_of[j] = the slot r_key[j] ends in (keyset_insert) and
+// first_row[slot] = min(j).  Items [n_r, n_r + n_wd): the walked directories'
+// keys into their set table.
 __global__ __launch_bounds__(kThreads) void k_idx_build(const uint64_t* __restrict__ r_key,
                                                         uint64_t n_r,
                                                         const uint64_t* __restrict__ wd_key,
@@ -119,18 +98,10 @@ __global__ __launch_bounds__(kThreads) void k_idx_build(const uint64_t* __restri
     const bool row = i < n_r;
     const uint64_t k = row ? r_key[i] : wd_key[i - n_r];
     uint64_t* t = row ? table : dtable;
-    const uint64_t m = (row ? cap : dcap) - 1;
-    uint64_t h = m + 1;
+    const uint64_t c = row ? cap : dcap;
+    uint64_t h = c;
     if (k != kEmptyKey) {
-      h = row_hash(k) & m;
-      for (;;) {
-        const unsigned long long prev =
-            atomicCAS(reinterpret_cast<unsigned long long*>(&t[h]),
-                      static_cast<unsigned long long>(kEmptyKey),
-                      static_cast<unsigned long long>(k));
-        if (prev == kEmptyKey || prev == k) break;
-        h = (h + 1) & m;
-      }
+      h = keyset_insert(t, c, k);
     } else if (!row) {
       hit[cap + 1] = 1;
     }
@@ -138,19 +109,6 @@ __global__ __launch_bounds__(kThreads) void k_idx_build(const uint64_t* __restri
       atomicMin(&first_row[h], static_cast<uint32_t>(i));
       slot_of[i] = static_cast<uint32_t>(h);
     }
-  }
-}
-
-// The slot of key k in a table of `cap` slots whose first probed slot holds
-// `sk`, or ~0 when the table does not hold it.  load < 1 (<= 1/2 up to 2^30
-// keys): an empty slot ends every walk.
-__device__ __forceinline__ uint64_t find_slot(const uint64_t* __restrict__ table, uint64_t cap,
-                                              uint64_t k, uint64_t h, uint64_t sk) {
-  for (;;) {
-    if (sk == k) return h;
-    if (sk == kEmptyKey) return ~0ull;
-    h = (h + 1) & (cap - 1);
-    sk = table[h];
   }
 }
 
@@ -194,7 +152,7 @@ __global__ __launch_bounds__(kThreads) void k_idx_probe(
     for (int u = 0; u < kWRows; ++u) {
       const uint64_t i = i0 + static_cast<uint64_t>(u) * kThreads;
       if (i >= n) continue;
-      const uint64_t slot = k[u] == kEmptyKey ? cap : find_slot(table, cap, k[u], h[u], s[u]);
+      const uint64_t slot = k[u] == kEmptyKey ? cap : keyset_find(table, cap, k[u], h[u], s[u]);
       // the key ~0: its slot exists always, first_row tells whether a row has it
       const uint32_t j0 = slot == ~0ull ? kMiss : first_row[slot];
       uint8_t st = kCreate;
@@ -251,7 +209,7 @@ __global__ __launch_bounds__(kThreads) void k_idx_rows(const uint64_t* __restric
       const uint64_t i = i0 + static_cast<uint64_t>(u) * kThreads;
       if (i >= n) continue;
       const bool in_set =
-          k[u] == kEmptyKey ? special : find_slot(dtable, dcap, k[u], h[u], s[u]) != ~0ull;
+          k[u] == kEmptyKey ? special : keyset_find(dtable, dcap, k[u], h[u], s[u]) != ~0ull;
       remove_flag[i] = in_set && b[u] == 0 ? 1 : 0;
     }
   }
@@ -276,21 +234,21 @@ __device__ __forceinline__ TileOf tile_of(const Lists& l, uint32_t b) {
   t.first = t.list * l.bw;
   t.src = t.list == 2 ? l.remove_flag : l.state;
   t.n = t.list == 2 ? l.n_r : l.n_w;
-  t.tile = static_cast<uint64_t>(b - t.first) * kCTile;
+  t.tile = static_cast<uint64_t>(b - t.first) * kTile;
   return t;
 }
 
-// A tile is kCRows x kThreads positions: position tile + k * kThreads + t, and
+// A tile is kRows x kThreads positions: position tile + k * kThreads + t, and
 // (k, t) order is index order.  Bit k of `f`: this thread's k-th position is
 // listed; of `kc`: it is a KIND_CHANGED entry (create tiles only).
 __device__ __forceinline__ void list_bits(const TileOf& t, uint32_t& f, uint32_t& kc) {
-  uint8_t v[kCRows];
+  uint8_t v[kRows];
 #pragma unroll
-  for (int k = 0; k < kCRows; ++k) v[k] = t.src[min(t.tile + k * kThreads + threadIdx.x, t.n - 1)];
+  for (int k = 0; k < kRows; ++k) v[k] = t.src[min(t.tile + k * kThreads + threadIdx.x, t.n - 1)];
   f = 0;
   kc = 0;
 #pragma unroll
-  for (int k = 0; k < kCRows; ++k) {
+  for (int k = 0; k < kRows; ++k) {
     const bool in = t.tile + k * kThreads + threadIdx.x < t.n;
     const bool on = t.list == 0 ? (v[k] == kCreate || v[k] == kKindChanged)
                                 : (t.list == 1 ? v[k] == kUpdate : v[k] != 0);
@@ -301,29 +259,13 @@ __device__ __forceinline__ void list_bits(const TileOf& t, uint32_t& f, uint32_t
 
 __global__ __launch_bounds__(kThreads) void k_idx_count(Lists l, uint32_t* __restrict__ cnt,
                                                         uint32_t* __restrict__ counts) {
-  __shared__ uint32_t sw[kCWaves][2];
   const TileOf t = tile_of(l, blockIdx.x);
-  uint32_t f, kc;
-  list_bits(t, f, kc);
-  uint32_t c = __popc(f), c3 = __popc(kc);
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    c += __shfl_xor(c, d);
-    c3 += __shfl_xor(c3, d);
-  }
-  if (__lane_id() == 0) {
-    sw[threadIdx.x >> 6][0] = c;
-    sw[threadIdx.x >> 6][1] = c3;
-  }
-  __syncthreads();
+  uint32_t f[2], a[2];  // listed, KIND_CHANGED
+  list_bits(t, f[0], f[1]);
+  compact::tile_count(f, a);
   if (threadIdx.x == 0) {
-    uint32_t a = 0, a3 = 0;
-    for (int w = 0; w < kCWaves; ++w) {
-      a += sw[w][0];
-      a3 += sw[w][1];
-    }
-    cnt[blockIdx.x] = a;
-    if (a3) atomicAdd(&counts[3], a3);  // counts[3] is zero on entry
+    cnt[blockIdx.x] = a[0];
+    if (a[1]) atomicAdd(&counts[3], a[1]);  // counts[3] is zero on entry
   }
 }
 
@@ -336,36 +278,16 @@ __global__ __launch_bounds__(kThreads) void k_idx_write(Lists l, uint32_t br,
                                                         uint32_t* __restrict__ update,
                                                         uint32_t* __restrict__ remove,
                                                         uint32_t* __restrict__ counts) {
-  __shared__ uint32_t off[kCRows][kCWaves];
+  __shared__ uint32_t off[kRows][kWaves];
   const TileOf t = tile_of(l, blockIdx.x);
   uint32_t* out = t.list == 0 ? create : (t.list == 1 ? update : remove);
-  const uint32_t lane = __lane_id(), w = threadIdx.x >> 6;
-  const uint64_t lt = (1ull << lane) - 1ull;
+  const uint32_t w = threadIdx.x >> 6;
   uint32_t f, kc;
   list_bits(t, f, kc);
-  uint32_t pre[kCRows];
+  uint32_t pre[kRows];
+  compact::tile_offsets(f, [&] { return offs[blockIdx.x] - offs[t.first]; }, off, pre);
 #pragma unroll
-  for (int k = 0; k < kCRows; ++k) {
-    const uint64_t b = __ballot(f >> k & 1u);
-    pre[k] = __popcll(b & lt);
-    if (lane == 0) off[k][w] = __popcll(b);
-  }
-  __syncthreads();
-  static_assert(kCRows * kCWaves == 64, "one wave scans the (row step, wave) counts");
-  if (threadIdx.x < 64) {  // (k, wave) order -- the array's order -- is index order
-    uint32_t* fl = &off[0][0];
-    const uint32_t a = fl[lane];
-    uint32_t inc = a;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t x = __shfl_up(inc, d);
-      if (lane >= static_cast<uint32_t>(d)) inc += x;
-    }
-    fl[lane] = offs[blockIdx.x] - offs[t.first] + inc - a;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < kCRows; ++k)
+  for (int k = 0; k < kRows; ++k)
     if (f >> k & 1u)
       out[off[k][w] + pre[k]] = static_cast<uint32_t>(t.tile + k * kThreads + threadIdx.x);
   if (blockIdx.x == 0 && threadIdx.x < 3) {
@@ -396,13 +318,13 @@ hipError_t indexer_diff_launch(const IndexerIn& in, uint32_t* match, uint8_t* st
   if (e != hipSuccess) return e;
   if (in.n_r + in.n_wd) {
     KScope k(timer, "idx_build", s);
-    k_idx_build<<<grid_for(in.n_r + in.n_wd, kThreads), kThreads, 0, s>>>(
+    k_idx_build<<<grid_for(in.n_r + in.n_wd, kThreads, kMaxGrid), kThreads, 0, s>>>(
         in.r_key, in.n_r, in.wd_key, in.n_wd, w.table, w.cap, w.dtable, w.dcap, w.first_row,
         w.slot_of, w.hit);
   }
   if (in.n_w) {
     KScope k(timer, "idx_probe", s);
-    const uint32_t grid = grid_for(in.n_w, kThreads * kWRows);
+    const uint32_t grid = grid_for(in.n_w, kThreads * kWRows, kMaxGrid);
 #define SD_IDX_PROBE(WF, RF)                                                                    \
   k_idx_probe<WF, RF><<<grid, kThreads, 0, s>>>(in.w_key, in.w_flags, in.w_meta, in.n_w,        \
                                                  w.table, w.cap, w.first_row, in.r_flags,       \
@@ -415,7 +337,7 @@ hipError_t indexer_diff_launch(const IndexerIn& in, uint32_t* match, uint8_t* st
   }
   if (in.n_r) {
     KScope k(timer, "idx_rows", s);
-    k_idx_rows<<<grid_for(in.n_r, kThreads * kRRows), kThreads, 0, s>>>(
+    k_idx_rows<<<grid_for(in.n_r, kThreads * kRRows, kMaxGrid), kThreads, 0, s>>>(
         in.r_dirkey, w.slot_of, in.n_r, w.dtable, w.dcap, w.hit, w.cap, w.remove_flag);
   }
   const Lists l{state, w.remove_flag, in.n_w, in.n_r, static_cast<uint32_t>(w.bw)};

@@ -36,6 +36,40 @@ struct KScope {
   }
 };
 
+// A workspace handed out in 256-byte-aligned pieces, in call order.  With a
+// null base every piece is null and bytes() is the size the pieces need, so one
+// function both sizes and lays out a workspace.
+class Carve {
+ public:
+  explicit Carve(void* base = nullptr) : p_(static_cast<uint8_t*>(base)) {}
+  // the next piece's offset from the base
+  size_t at(size_t bytes) {
+    const size_t a = o_;
+    o_ += (bytes + 255) / 256 * 256;
+    return a;
+  }
+  uint8_t* take(size_t bytes) {
+    const size_t a = at(bytes);
+    return p_ ? p_ + a : nullptr;
+  }
+  template <class T>
+  T* take(size_t count) {
+    return reinterpret_cast<T*>(take(count * sizeof(T)));
+  }
+  size_t bytes() const { return o_; }
+
+ private:
+  uint8_t* p_;
+  size_t o_ = 0;
+};
+
+// Workgroups for n items at `per` a workgroup: at least one, at most `most`
+// (the kernels stride over the rest).
+inline uint32_t grid_for(uint64_t n, uint64_t per, uint32_t most) {
+  const uint64_t g = (n + per - 1) / per;
+  return static_cast<uint32_t>(g == 0 ? 1 : (g < most ? g : most));
+}
+
 // ---- batched short-message BLAKE3 (cas_id, K1) ------------------------------
 // Workspace for one batch of n messages and at most max_chunks chunks.
 struct BatchWork {

@@ -14,6 +14,7 @@
 // hash failed, mod.rs:113,127) are in neither list: they stay orphans.
 // HBM-bound: reads 9 B/row twice, writes 4 B per created row and 8 B per
 // linked row; three launches + a scan of two counters per 4096-row tile.
+#include "compact_device.hpp"
 #include "internal.hpp"
 #include "scan_device.hpp"
 
@@ -21,13 +22,14 @@ namespace sdgpu {
 
 namespace {
 
-// A block takes a tile of kTile rows: row tile + k * kThreads + t for k in
-// [0, kRows) -- coalesced loads, and (k, t) order is row order, so in-block
-// ranks from per-(k, wave) ballots keep both lists in row order.
-constexpr int kThreads = 256;
-constexpr int kRows = 16;
-constexpr uint32_t kTile = kThreads * kRows;
-constexpr int kWaves = kThreads / 64;
+// A block takes a tile of the shared compaction (compact_device.hpp): row
+// tile + k * kThreads + t for k in [0, kRows); both lists are ranked in one go.
+using compact::kRows;
+using compact::kThreads;
+using compact::kTile;
+using compact::kWaves;
+using compact::wave_scan;
+using compact::wave_sum;
 
 struct LinkRow {
   uint32_t r, p;
@@ -78,35 +80,20 @@ __global__ __launch_bounds__(kThreads) void k_link_count(const uint32_t* __restr
                                                          const uint8_t* __restrict__ valid,
                                                          uint32_t first_rank, uint64_t n,
                                                          uint32_t nb, uint32_t* __restrict__ cnt) {
-  __shared__ uint32_t sc[kWaves], sl[kWaves];
   const uint64_t tile = static_cast<uint64_t>(blockIdx.x) * kTile;
-  uint32_t c = 0, l = 0;
+  uint32_t f[2] = {0, 0}, t[2];  // creators, connectors
   LinkRows q;
   link_load(rep, rank, valid, n, tile, q);
 #pragma unroll
   for (int k = 0; k < kRows; ++k) {
     const LinkRow x = link_row(q, k, rank, valid, first_rank, n, tile + k * kThreads + threadIdx.x);
-    c += x.c;
-    l += x.l;
+    f[0] |= (x.c ? 1u : 0u) << k;
+    f[1] |= (x.l ? 1u : 0u) << k;
   }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    c += __shfl_xor(c, d);
-    l += __shfl_xor(l, d);
-  }
-  if (__lane_id() == 0) {
-    sc[threadIdx.x >> 6] = c;
-    sl[threadIdx.x >> 6] = l;
-  }
-  __syncthreads();
+  compact::tile_count(f, t);
   if (threadIdx.x == 0) {
-    uint32_t tc = 0, tl = 0;
-    for (int w = 0; w < kWaves; ++w) {
-      tc += sc[w];
-      tl += sl[w];
-    }
-    cnt[blockIdx.x] = tc;
-    cnt[nb + blockIdx.x] = tl;
+    cnt[blockIdx.x] = t[0];
+    cnt[nb + blockIdx.x] = t[1];
   }
 }
 
@@ -117,61 +104,38 @@ __global__ __launch_bounds__(kThreads) void k_link_write(
     const uint8_t* __restrict__ valid, uint32_t first_rank, uint64_t n, uint32_t nb,
     const uint32_t* __restrict__ cnt, uint32_t* __restrict__ create, uint32_t* __restrict__ link_row_out,
     uint32_t* __restrict__ link_obj, uint32_t* __restrict__ d_counts) {
-  __shared__ uint32_t oc[kRows][kWaves], ol[kRows][kWaves];
+  __shared__ uint32_t off[2][kRows][kWaves];  // creators, connectors
   const uint64_t tile = static_cast<uint64_t>(blockIdx.x) * kTile;
-  const uint32_t lane = __lane_id(), w = threadIdx.x >> 6;
-  const uint64_t lt = (1ull << lane) - 1ull;
+  const uint32_t w = threadIdx.x >> 6;
   const uint32_t total_c = cnt[nb];
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     d_counts[0] = total_c;
     d_counts[1] = cnt[2 * static_cast<uint64_t>(nb)] - total_c;
   }
   LinkRow x[kRows];
-  uint32_t pc[kRows], pl[kRows];
+  uint32_t f[2] = {0, 0}, pre[2][kRows];
   LinkRows q;
   link_load(rep, rank, valid, n, tile, q);
 #pragma unroll
   for (int k = 0; k < kRows; ++k) {
     x[k] = link_row(q, k, rank, valid, first_rank, n, tile + k * kThreads + threadIdx.x);
-    const uint64_t bc = __ballot(x[k].c), bl = __ballot(x[k].l);
-    pc[k] = __popcll(bc & lt);
-    pl[k] = __popcll(bl & lt);
-    if (lane == 0) {
-      oc[k][w] = __popcll(bc);
-      ol[k][w] = __popcll(bl);
-    }
+    f[0] |= (x[k].c ? 1u : 0u) << k;
+    f[1] |= (x[k].l ? 1u : 0u) << k;
   }
-  __syncthreads();
-  static_assert(kRows * kWaves == 64, "one wave scans the (row step, wave) counts");
-  if (threadIdx.x < 64) {  // (k, wave) order -- k-major, the array's order -- is row order
-    uint32_t* fc = &oc[0][0];
-    uint32_t* fl = &ol[0][0];
-    const uint32_t a = fc[lane], b = fl[lane];
-    uint32_t ic = a, il = b;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t xc = __shfl_up(ic, d), xl = __shfl_up(il, d);
-      if (lane >= static_cast<uint32_t>(d)) {
-        ic += xc;
-        il += xl;
-      }
-    }
-    fc[lane] = cnt[blockIdx.x] + ic - a;
-    fl[lane] = cnt[nb + blockIdx.x] - total_c + il - b;
-  }
-  __syncthreads();
+  compact::tile_offsets(
+      f, [&](int i) { return i == 0 ? cnt[blockIdx.x] : cnt[nb + blockIdx.x] - total_c; }, off, pre);
 #pragma unroll
   for (int k = 0; k < kRows; ++k) {
-    if (x[k].c) create[oc[k][w] + pc[k]] = x[k].r;
+    if (x[k].c) create[off[0][k][w] + pre[0][k]] = x[k].r;
     if (x[k].l) {
-      const uint32_t q = ol[k][w] + pl[k];
+      const uint32_t q = off[1][k][w] + pre[1][k];
       link_row_out[q] = x[k].r;
       link_obj[q] = x[k].p;
     }
   }
 }
 
-inline uint32_t link_tiles(uint64_t n) { return static_cast<uint32_t>((n + kTile - 1) / kTile); }
+inline uint32_t link_tiles(uint64_t n) { return static_cast<uint32_t>(compact::tiles_for(n)); }
 
 // Entries of the fused write set that are not in the bucket records
 // (sdgpu_group_link_device), appended in row order after the keyed entries
@@ -274,11 +238,8 @@ __global__ __launch_bounds__(kThreads) void k_extra_count(
       l += extra_linked(true, hitrep, i0 + k, rank_of(rank, first_rank, i0 + k), o) ? 1u : 0u;
     }
   }
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) {
-    c += __shfl_xor(c, s);
-    l += __shfl_xor(l, s);
-  }
+  c = wave_sum(c);
+  l = wave_sum(l);
   if (__lane_id() == 0) {
     sc[threadIdx.x >> 6] = c;
     sl[threadIdx.x >> 6] = l;
@@ -315,15 +276,7 @@ __global__ __launch_bounds__(kScanThreads) void k_extra_scan(uint32_t* __restric
   }
   // block-wide exclusive scan of t (wave scan + wave totals)
   const uint32_t lane = __lane_id(), w = threadIdx.x >> 6;
-  uint32_t inc = t;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(inc, d);
-    if (lane >= static_cast<uint32_t>(d)) inc += o;
-  }
-  uint32_t lw = l;
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) lw += __shfl_xor(lw, d);
+  const uint32_t inc = wave_scan(t), lw = wave_sum(l);
   if (lane == 63) sw[w] = inc;
   if (lane == 0) slk[w] = lw;
   __syncthreads();
@@ -364,12 +317,7 @@ __global__ __launch_bounds__(kThreads) void k_extra_write(
     uint32_t hm;
     uint32_t m = extra_mask(has, valid, grouped, n, i0, hm);
     const uint32_t c = __popc(m);
-    uint32_t inc = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t o = __shfl_up(inc, d);
-      if (lane >= static_cast<uint32_t>(d)) inc += o;
-    }
+    const uint32_t inc = wave_scan(c);
     if (lane == 63) sw[wv] = inc;
     __syncthreads();
     uint32_t pos = base + inc - c, tile_total = 0;

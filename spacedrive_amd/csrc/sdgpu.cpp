@@ -1864,19 +1864,15 @@ int sdgpu_indexer_diff(sdgpu_ctx* c, const uint64_t* w_key, const uint8_t* w_fla
   hipStream_t s = pick(c, nullptr);
   // workspace | the inputs | matched, state, create, update, remove, counts in
   // the context's link workspace
-  size_t o = align_up(indexer_workspace_bytes(n_w, n_wd, n_r), 256);
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o += align_up(bytes, 256);
-    return at;
-  };
-  const size_t o_wk = take(8 * n_w), o_wf = take(w_flags ? n_w : 0), o_wm = take(24 * n_w);
-  const size_t o_dk = take(8 * n_wd);
-  const size_t o_rk = take(8 * n_r), o_rd = take(8 * n_r), o_rf = take(r_flags ? n_r : 0);
-  const size_t o_rm = take(24 * n_r);
-  const size_t o_ma = take(4 * n_w), o_st = take(n_w), o_cr = take(4 * n_w), o_up = take(4 * n_w);
-  const size_t o_re = take(4 * n_r), o_cn = take(4 * 4);
-  SD_TRY_RC(ensure_dev(c, c->link_ws, o));
+  Carve cv;
+  cv.at(indexer_workspace_bytes(n_w, n_wd, n_r));
+  const size_t o_wk = cv.at(8 * n_w), o_wf = cv.at(w_flags ? n_w : 0), o_wm = cv.at(24 * n_w);
+  const size_t o_dk = cv.at(8 * n_wd);
+  const size_t o_rk = cv.at(8 * n_r), o_rd = cv.at(8 * n_r), o_rf = cv.at(r_flags ? n_r : 0);
+  const size_t o_rm = cv.at(24 * n_r);
+  const size_t o_ma = cv.at(4 * n_w), o_st = cv.at(n_w), o_cr = cv.at(4 * n_w);
+  const size_t o_up = cv.at(4 * n_w), o_re = cv.at(4 * n_r), o_cn = cv.at(4 * 4);
+  SD_TRY_RC(ensure_dev(c, c->link_ws, cv.bytes()));
   uint8_t* base = static_cast<uint8_t*>(c->link_ws.p);
   auto u64p = [&](size_t at) { return reinterpret_cast<uint64_t*>(base + at); };
   auto u32p = [&](size_t at) { return reinterpret_cast<uint32_t*>(base + at); };
@@ -2054,21 +2050,19 @@ int sdgpu_search_page(sdgpu_ctx* c, const sdgpu_search_rows_t* rows,
   const uint64_t np = need.pairs ? objects->n_pairs : 0;
   // workspace | the columns the query uses | page, counts in the context's link
   // workspace
-  size_t o = align_up(search_workspace_bytes(n, m), 256);
-  auto take = [&](bool on, size_t bytes) {
-    const size_t at = o;
-    if (on) o += align_up(bytes, 256);
-    return at;
-  };
-  const size_t o_loc = take(need.location, 4 * n), o_ext = take(need.ext, 2 * n);
-  const size_t o_dir = take(need.dir_key, 8 * n), o_fl = take(need.flags, n);
-  const size_t o_dc = take(need.date_created, 8 * n), o_obj = take(need.object, 4 * n);
-  const size_t o_el = take(need.eligible, n), o_ok = take(need.order_key, 8 * n);
-  const size_t o_kind = take(need.kind, 4 * m), o_ofl = take(need.oflags, m);
-  const size_t o_da = take(need.date_accessed, 8 * m), o_ook = take(need.o_order_key, 8 * m);
-  const size_t o_to = take(need.pairs, 4 * np), o_tt = take(need.pairs, 4 * np);
-  const size_t o_page = take(true, 4 * SDGPU_SEARCH_MAX_TAKE), o_cnt = take(true, 4 * 4);
-  SD_TRY_RC(ensure_dev(c, c->link_ws, o));
+  Carve cv;
+  cv.at(search_workspace_bytes(n, m));
+  const size_t o_loc = cv.at(need.location ? 4 * n : 0), o_ext = cv.at(need.ext ? 2 * n : 0);
+  const size_t o_dir = cv.at(need.dir_key ? 8 * n : 0), o_fl = cv.at(need.flags ? n : 0);
+  const size_t o_dc = cv.at(need.date_created ? 8 * n : 0);
+  const size_t o_obj = cv.at(need.object ? 4 * n : 0);
+  const size_t o_el = cv.at(need.eligible ? n : 0), o_ok = cv.at(need.order_key ? 8 * n : 0);
+  const size_t o_kind = cv.at(need.kind ? 4 * m : 0), o_ofl = cv.at(need.oflags ? m : 0);
+  const size_t o_da = cv.at(need.date_accessed ? 8 * m : 0);
+  const size_t o_ook = cv.at(need.o_order_key ? 8 * m : 0);
+  const size_t o_to = cv.at(need.pairs ? 4 * np : 0), o_tt = cv.at(need.pairs ? 4 * np : 0);
+  const size_t o_page = cv.at(4 * SDGPU_SEARCH_MAX_TAKE), o_cnt = cv.at(4 * 4);
+  SD_TRY_RC(ensure_dev(c, c->link_ws, cv.bytes()));
   uint8_t* base = static_cast<uint8_t*>(c->link_ws.p);
   sdgpu_search_rows_t dr{};
   sdgpu_search_objects_t dobj{};

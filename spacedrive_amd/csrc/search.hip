@@ -88,28 +88,17 @@ struct SearchWs {
 
 SearchWs search_ws(uint64_t n, uint64_t m, void* ws) {
   SearchWs w;
-  uint8_t* p = static_cast<uint8_t*>(ws);
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    uint8_t* q = p ? p + o : nullptr;
-    o += (bytes + 255) / 256 * 256;
-    return q;
-  };
-  w.mark = take(m);
-  w.ctl = reinterpret_cast<SelCtl*>(take(2 * sizeof(SelCtl)));
+  Carve c(ws);
+  w.mark = c.take(m);
+  w.ctl = c.take<SelCtl>(2);
   for (int b = 0; b < 3; ++b) {
-    w.key[b] = reinterpret_cast<uint64_t*>(take(8 * n));
-    w.row[b] = reinterpret_cast<uint32_t*>(take(4 * n));
+    w.key[b] = c.take<uint64_t>(n);
+    w.row[b] = c.take<uint32_t>(n);
   }
-  w.wkey = reinterpret_cast<uint64_t*>(take(8 * kMaxTake));
-  w.wrow = reinterpret_cast<uint32_t*>(take(4 * kMaxTake));
-  w.bytes = o;
+  w.wkey = c.take<uint64_t>(kMaxTake);
+  w.wrow = c.take<uint32_t>(kMaxTake);
+  w.bytes = c.bytes();
   return w;
-}
-
-uint32_t grid_for(uint64_t n, uint64_t per, uint32_t most) {
-  const uint64_t g = (n + per - 1) / per;
-  return static_cast<uint32_t>(g == 0 ? 1 : (g < most ? g : most));
 }
 
 // Device pointers and operands of one call, by value.

@@ -1646,16 +1646,12 @@ int sync_ingest_host_run(sdgpu_oplog* x, const uint64_t* key, const uint64_t* ta
   // and the two lists come back in copies of their own once their lengths are
   // known -- nine copy commands around the launches, which a 1000-op page pays
   // in full
-  size_t o = align_up(sync_ingest_workspace_bytes(n), 256);
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o += align_up(bytes, 256);
-    return at;
-  };
-  const size_t o_k = take(8 * n), o_t = take(8 * n), o_ts = take(8 * n);
-  const size_t o_in = take(instance ? 4 * n : 0), o_cl = take(8ull * n_instances);
-  const size_t o_ap = take(n), o_al = take(4 * n), o_wl = take(4 * n), o_cn = take(4 * 4);
-  SD_TRY_RC(ensure_dev(c, c->link_ws, o));
+  Carve cv;
+  cv.at(sync_ingest_workspace_bytes(n));
+  const size_t o_k = cv.at(8 * n), o_t = cv.at(8 * n), o_ts = cv.at(8 * n);
+  const size_t o_in = cv.at(instance ? 4 * n : 0), o_cl = cv.at(8ull * n_instances);
+  const size_t o_ap = cv.at(n), o_al = cv.at(4 * n), o_wl = cv.at(4 * n), o_cn = cv.at(4 * 4);
+  SD_TRY_RC(ensure_dev(c, c->link_ws, cv.bytes()));
   uint8_t* base = static_cast<uint8_t*>(c->link_ws.p);
   auto u64p = [&](size_t at) { return reinterpret_cast<uint64_t*>(base + at); };
   auto u32p = [&](size_t at) { return reinterpret_cast<uint32_t*>(base + at); };

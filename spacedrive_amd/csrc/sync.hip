@@ -12,8 +12,8 @@
 // Here: the op log is an open-addressing table that lives as long as the
 // library (32-byte slots {key, timestamp, tag, spare}: a probe costs one
 // sector; capacity a power of two, linear probing from row_hash(key), empty
-// slot ~0; the key ~0 owns the slot one past the table, as index.hip and
-// indexer.hip do it).  The timestamp is stored biased by 1 << 63, so unsigned
+// slot ~0; the key ~0 owns the slot one past the table, the convention of
+// keyset_device.hpp's 8-byte sets).  The timestamp is stored biased by 1 << 63, so unsigned
 // 64-bit order is the signed order and the empty value 0 is INT64_MIN.  A page:
 //   k_log_slot   one lane per op: probe or insert the key; slot_of[i], the
 //                slot's logged timestamp base[i]; new keys counted from wave
@@ -30,7 +30,9 @@
 //                marks the winner; tiles are joined by an aggregate pass and a
 //                one-workgroup scan of the aggregates;
 //   k_ing_count / scan / k_ing_write
-//                applied and winner as ONE compaction (indexer.hip's layout).
+//                applied and winner as ONE compaction (compact_device.hpp; the
+//                two lists' tiles behind one another, one scan).
+#include "compact_device.hpp"
 #include "internal.hpp"
 #include "rows_device.hpp"
 #include "scan_device.hpp"
@@ -51,24 +53,13 @@ constexpr int kRounds = 8;
 constexpr uint32_t kTile = kRounds * kThreads;  // 2048
 constexpr uint32_t kBins = 256;
 
-constexpr int kCRows = 16;  // compaction: positions per thread
-constexpr uint64_t kCTile = static_cast<uint64_t>(kCRows) * kThreads;
-constexpr int kCWaves = kThreads / 64;
+static_assert(kThreads == compact::kThreads, "k_ing_count / k_ing_write");
+constexpr uint32_t kMaxGrid = 4096;
+using compact::wave_sum;
 
 // slot s of the table: words [4 s, 4 s + 4) = key, biased timestamp, tag, spare
 __device__ __forceinline__ uint64_t* slot_at(const OplogRef& t, uint64_t s) {
   return t.slots + 4 * s;
-}
-
-uint32_t grid_for(uint64_t n, uint64_t per) {
-  const uint64_t g = (n + per - 1) / per;
-  return static_cast<uint32_t>(g == 0 ? 1 : (g < 4096 ? g : 4096));
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-  return v;
 }
 
 // Every slot empty (key ~0, timestamp 0 = none, tag 0), the key ~0's slot
@@ -516,16 +507,16 @@ __global__ __launch_bounds__(kThreads) void k_seg_apply(
 }
 
 // ---- applied and winner as one compaction -------------------------------------------
-// Blocks [0, bt) list apply[n], [bt, 2 bt) win[n]; a tile is kCRows x kThreads
+// Blocks [0, bt) list apply[n], [bt, 2 bt) win[n]; a tile is compact::kRows x kThreads
 // positions, position tile + k * kThreads + t, and (k, t) order is index order.
 __device__ __forceinline__ uint32_t list_bits(const uint8_t* __restrict__ src, uint64_t n,
                                               uint64_t tile) {
-  uint8_t v[kCRows];
+  uint8_t v[compact::kRows];
 #pragma unroll
-  for (int k = 0; k < kCRows; ++k) v[k] = src[min(tile + k * kThreads + threadIdx.x, n - 1)];
+  for (int k = 0; k < compact::kRows; ++k) v[k] = src[min(tile + k * kThreads + threadIdx.x, n - 1)];
   uint32_t f = 0;
 #pragma unroll
-  for (int k = 0; k < kCRows; ++k)
+  for (int k = 0; k < compact::kRows; ++k)
     f |= (tile + k * kThreads + threadIdx.x < n && v[k] != 0 ? 1u : 0u) << k;
   return f;
 }
@@ -534,18 +525,11 @@ __global__ __launch_bounds__(kThreads) void k_ing_count(const uint8_t* __restric
                                                         const uint8_t* __restrict__ win,
                                                         uint64_t n, uint32_t bt,
                                                         uint32_t* __restrict__ cnt) {
-  __shared__ uint32_t sw[kCWaves];
   const bool second = blockIdx.x >= bt;
-  const uint32_t f =
-      list_bits(second ? win : apply, n, static_cast<uint64_t>(blockIdx.x - (second ? bt : 0)) * kCTile);
-  const uint32_t c = wave_sum(__popc(f));
-  if (__lane_id() == 0) sw[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t a = 0;
-    for (int w = 0; w < kCWaves; ++w) a += sw[w];
-    cnt[blockIdx.x] = a;
-  }
+  const uint32_t f = list_bits(second ? win : apply, n,
+                               static_cast<uint64_t>(blockIdx.x - (second ? bt : 0)) * compact::kTile);
+  const uint32_t a = compact::tile_count(f);
+  if (threadIdx.x == 0) cnt[blockIdx.x] = a;
 }
 
 __global__ __launch_bounds__(kThreads) void k_ing_write(const uint8_t* __restrict__ apply,
@@ -555,37 +539,17 @@ __global__ __launch_bounds__(kThreads) void k_ing_write(const uint8_t* __restric
                                                         uint32_t* __restrict__ applied,
                                                         uint32_t* __restrict__ winner,
                                                         uint32_t* __restrict__ counts) {
-  __shared__ uint32_t off[kCRows][kCWaves];
+  __shared__ uint32_t off[compact::kRows][compact::kWaves];
   const bool second = blockIdx.x >= bt;
   const uint32_t first = second ? bt : 0;
-  const uint64_t tile = static_cast<uint64_t>(blockIdx.x - first) * kCTile;
+  const uint64_t tile = static_cast<uint64_t>(blockIdx.x - first) * compact::kTile;
   uint32_t* out = second ? winner : applied;
-  const uint32_t lane = __lane_id(), w = threadIdx.x >> 6;
-  const uint64_t lt = (1ull << lane) - 1ull;
+  const uint32_t w = threadIdx.x >> 6;
   const uint32_t f = list_bits(second ? win : apply, n, tile);
-  uint32_t pre[kCRows];
+  uint32_t pre[compact::kRows];
+  compact::tile_offsets(f, [&] { return offs[blockIdx.x] - offs[first]; }, off, pre);
 #pragma unroll
-  for (int k = 0; k < kCRows; ++k) {
-    const uint64_t b = __ballot(f >> k & 1u);
-    pre[k] = __popcll(b & lt);
-    if (lane == 0) off[k][w] = __popcll(b);
-  }
-  __syncthreads();
-  static_assert(kCRows * kCWaves == 64, "one wave scans the (row step, wave) counts");
-  if (threadIdx.x < 64) {  // (k, wave) order -- the array's order -- is index order
-    uint32_t* fl = &off[0][0];
-    const uint32_t a = fl[lane];
-    uint32_t inc = a;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t x = __shfl_up(inc, d);
-      if (lane >= static_cast<uint32_t>(d)) inc += x;
-    }
-    fl[lane] = offs[blockIdx.x] - offs[first] + inc - a;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < kCRows; ++k)
+  for (int k = 0; k < compact::kRows; ++k)
     if (f >> k & 1u)
       out[off[k][w] + pre[k]] = static_cast<uint32_t>(tile + k * kThreads + threadIdx.x);
   if (blockIdx.x == 0 && threadIdx.x < 2)
@@ -609,28 +573,21 @@ struct IngWs {
 
 IngWs ing_ws(uint64_t n, void* ws) {
   IngWs w;
-  uint8_t* p = static_cast<uint8_t*>(ws);
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    uint8_t* q = p ? p + o : nullptr;
-    o += (bytes + 255) / 256 * 256;
-    return q;
-  };
+  Carve c(ws);
   w.tiles = static_cast<uint32_t>((n + kTile - 1) / kTile);
-  w.bt = static_cast<uint32_t>((n + kCTile - 1) / kCTile);
-  w.slot_of = reinterpret_cast<uint32_t*>(take(4 * n));
-  w.base = reinterpret_cast<uint64_t*>(take(8 * n));
-  w.pair[0] = reinterpret_cast<uint2*>(take(8 * n));
-  w.pair[1] = reinterpret_cast<uint2*>(take(8 * n));
-  w.win = take(n);
+  w.bt = static_cast<uint32_t>(compact::tiles_for(n));
+  w.slot_of = c.take<uint32_t>(n);
+  w.base = c.take<uint64_t>(n);
+  w.pair[0] = c.take<uint2>(n);
+  w.pair[1] = c.take<uint2>(n);
+  w.win = c.take(n);
   const uint64_t nh = static_cast<uint64_t>(kBins) * w.tiles;
-  w.cnt = reinterpret_cast<uint32_t*>(take(4 * (nh + 1)));
-  w.cnt_sums = reinterpret_cast<uint32_t*>(take(4 * (static_cast<size_t>(scan::tiles_for(nh)) + 1)));
-  w.agg = reinterpret_cast<Seg*>(take(sizeof(Seg) * w.tiles));
-  w.lcnt = reinterpret_cast<uint32_t*>(take(4 * (2ull * w.bt + 1)));
-  w.lcnt_sums =
-      reinterpret_cast<uint32_t*>(take(4 * (static_cast<size_t>(scan::tiles_for(2ull * w.bt)) + 1)));
-  w.bytes = o;
+  w.cnt = c.take<uint32_t>(nh + 1);
+  w.cnt_sums = c.take<uint32_t>(static_cast<size_t>(scan::tiles_for(nh)) + 1);
+  w.agg = c.take<Seg>(w.tiles);
+  w.lcnt = c.take<uint32_t>(2ull * w.bt + 1);
+  w.lcnt_sums = c.take<uint32_t>(static_cast<size_t>(scan::tiles_for(2ull * w.bt)) + 1);
+  w.bytes = c.bytes();
   return w;
 }
 
@@ -643,13 +600,13 @@ uint32_t oplog_sort_passes(uint64_t cap) {
 }
 
 hipError_t oplog_clear_launch(const OplogRef& t, hipStream_t s) {
-  k_log_clear<<<grid_for(t.cap + 1, kThreads), kThreads, 0, s>>>(t);
+  k_log_clear<<<grid_for(t.cap + 1, kThreads, kMaxGrid), kThreads, 0, s>>>(t);
   return hipGetLastError();
 }
 
 hipError_t oplog_rehash_launch(const OplogRef& from, const OplogRef& to, hipStream_t s) {
-  k_log_clear<<<grid_for(to.cap + 1, kThreads), kThreads, 0, s>>>(to);
-  k_log_rehash<<<grid_for(from.cap + 1, kThreads), kThreads, 0, s>>>(from, to);
+  k_log_clear<<<grid_for(to.cap + 1, kThreads, kMaxGrid), kThreads, 0, s>>>(to);
+  k_log_rehash<<<grid_for(from.cap + 1, kThreads, kMaxGrid), kThreads, 0, s>>>(from, to);
   return hipGetLastError();
 }
 
@@ -666,11 +623,11 @@ hipError_t oplog_add_launch(const OplogRef& t, const uint64_t* key, const uint64
   uint32_t* slot_of = collisions ? static_cast<uint32_t*>(ws) : nullptr;
   {
     KScope k(timer, "log_add", s);
-    k_log_add<<<grid_for(n, kThreads), kThreads, 0, s>>>(t, key, tag, ts, n, slot_of);
+    k_log_add<<<grid_for(n, kThreads, kMaxGrid), kThreads, 0, s>>>(t, key, tag, ts, n, slot_of);
   }
   if (collisions) {
     KScope k(timer, "log_tags", s);
-    k_log_tags<<<grid_for(n, kThreads), kThreads, 0, s>>>(t, tag, slot_of, n, collisions);
+    k_log_tags<<<grid_for(n, kThreads, kMaxGrid), kThreads, 0, s>>>(t, tag, slot_of, n, collisions);
   }
   return hipGetLastError();
 }
@@ -679,7 +636,7 @@ hipError_t oplog_latest_launch(const OplogRef& t, const uint64_t* key, uint64_t 
                                uint8_t* found, hipStream_t s, KTimer* timer) {
   if (n == 0) return hipSuccess;
   KScope k(timer, "log_latest", s);
-  k_log_latest<<<grid_for(n, kThreads), kThreads, 0, s>>>(t, key, n, ts, found);
+  k_log_latest<<<grid_for(n, kThreads, kMaxGrid), kThreads, 0, s>>>(t, key, n, ts, found);
   return hipGetLastError();
 }
 
@@ -697,7 +654,7 @@ hipError_t sync_ingest_launch(const OplogRef& t, const uint64_t* key, const uint
   if (e != hipSuccess) return e;
   {
     KScope k(timer, "ing_slot", s);
-    k_log_slot<<<grid_for(n, kThreads), kThreads, 0, s>>>(t, key, tag, ts, instance, n, clock,
+    k_log_slot<<<grid_for(n, kThreads, kMaxGrid), kThreads, 0, s>>>(t, key, tag, ts, instance, n, clock,
                                                           n_instances, w.slot_of, w.base, counts);
   }
   const uint32_t passes = oplog_sort_passes(t.cap);

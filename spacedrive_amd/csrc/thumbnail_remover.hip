@@ -9,35 +9,36 @@
 // thumbnails holds, unlinks the rest, and removes a directory when everything
 // it found there went.
 //
-// Here the table is built on the SMALL side: the thumbnail keys go into an
-// open-addressing table in the context's workspace (8-byte slots, capacity a
-// power of two >= 2 x n_thumbs, linear probing from row_hash(key), empty slot
-// ~0; the key ~0 itself owns the slot one past the table, as index.hip does
-// it), every thumbnail remembers the slot it ended in (slot_of), and the LARGE
-// side -- the cas key columns of the file_paths, plus the non-indexed set as
-// one more column -- is streamed once: a row whose key sits in the table
-// stores hit[slot] = 1, a plain byte store (idempotent: no atomics in that
-// pass); a one-bit-per-hash filter in front of the table keeps most rows that
-// own no thumbnail out of it (k_stale_probe).  The thumbnails whose slot was not hit are then compacted in list
-// order (4096-row tiles: count, one scan of the tile counts, in-tile ballot
-// ranks -- k_orphan_count / k_orphan_write's scheme), and every directory
-// boundary gets its offset into that list from its tile's offset plus a count
-// of the tile's rows before it.  A key listed twice (a misplaced copy in a
+// Here the table is built on the SMALL side: the thumbnail keys go into a key
+// set in the context's workspace (keyset_device.hpp: 8-byte slots, the key ~0
+// owns the slot one past the table), every thumbnail remembers the slot it
+// ended in (slot_of), and the LARGE side -- the cas key columns of the
+// file_paths, plus the non-indexed set as one more column -- is streamed once:
+// a row whose key sits in the table stores hit[slot] = 1, a plain byte store
+// (idempotent: no atomics in that pass); a one-bit-per-hash filter in front of
+// the table keeps most rows that own no thumbnail out of it (k_stale_probe).
+// The thumbnails whose slot was not hit are then compacted in list order (the
+// shared tile compaction of compact_device.hpp), and every directory boundary
+// gets its offset into that list from its tile's offset plus a count of the
+// tile's rows before it.  A key listed twice (a misplaced copy in a
 // second directory) ends in one slot, so both copies get one answer.
 //
 // The same table answers the opposite question, which file_paths still need a
 // thumbnail (thumbnailer.hip): k_thumb_present probes it per row.
+#include "compact_device.hpp"
 #include "internal.hpp"
-#include "rows_device.hpp"
+#include "keyset_device.hpp"
 #include "scan_device.hpp"
 
 namespace sdgpu {
 
 namespace {
 
-constexpr uint64_t kEmptyKey = ~0ull;
-constexpr int kThreads = 256;
-constexpr uint64_t kMinCap = 1024;
+using compact::kRows;
+using compact::kThreads;
+using compact::kTile;
+using compact::kWaves;
+constexpr uint32_t kMaxGrid = 2048;
 
 struct StaleWs {
   uint64_t cap;       // slots; the key ~0 owns slot `cap`
@@ -50,45 +51,22 @@ struct StaleWs {
   size_t bytes;
 };
 
-uint64_t stale_cap(uint64_t n) {
-  uint64_t cap = kMinCap;
-  // 2^31 slots at the most: a slot number, the special one included, is a u32
-  while (cap < 2 * n && cap < (1ull << 31)) cap <<= 1;
-  return cap;
-}
-
-constexpr int kSRows = 16;
-constexpr uint64_t kSTile = static_cast<uint64_t>(kSRows) * kThreads;
-constexpr int kSWaves = kThreads / 64;
-
 StaleWs stale_ws(uint64_t n, void* ws) {
   StaleWs w;
-  w.cap = stale_cap(n);
-  const uint64_t blocks = (n + kSTile - 1) / kSTile;
-  uint8_t* p = static_cast<uint8_t*>(ws);
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    uint8_t* q = p ? p + o : nullptr;
-    o += (bytes + 255) / 256 * 256;
-    return q;
-  };
-  w.table = reinterpret_cast<uint64_t*>(take(8 * w.cap));
-  w.hit = take(w.cap + 2);
-  w.bits = reinterpret_cast<uint32_t*>(take(w.cap));
-  w.slot_of = reinterpret_cast<uint32_t*>(take(4 * n));
-  w.cnt = reinterpret_cast<uint32_t*>(take(4 * (blocks + 1)));
-  w.tiles = reinterpret_cast<uint32_t*>(take(4 * (static_cast<size_t>(scan::tiles_for(blocks)) + 1)));
-  w.bytes = o;
+  w.cap = keyset_cap(n);
+  const uint64_t blocks = compact::tiles_for(n);
+  Carve c(ws);
+  w.table = c.take<uint64_t>(w.cap);
+  w.hit = c.take(w.cap + 2);
+  w.bits = c.take<uint32_t>(w.cap / 4);
+  w.slot_of = c.take<uint32_t>(n);
+  w.cnt = c.take<uint32_t>(blocks + 1);
+  w.tiles = c.take<uint32_t>(static_cast<size_t>(scan::tiles_for(blocks)) + 1);
+  w.bytes = c.bytes();
   return w;
 }
 
-uint32_t grid_for(uint64_t n, uint64_t per) {
-  const uint64_t g = (n + per - 1) / per;
-  return static_cast<uint32_t>(g == 0 ? 1 : (g < 2048 ? g : 2048));
-}
-
-// slot_of[i] = the slot thumbnail key[i] ends in: the first thread to claim an
-// empty slot (64-bit CAS) places the key, every other copy of it finds it.
+// slot_of[i] = the slot thumbnail key[i] ends in (keyset_insert).
 // Also sets the key's filter bit (one atomicOr per thumbnail), and for the key
 // ~0, which has no slot in the table, the byte hit[cap + 1] that tells
 // k_thumb_present the thumbnail exists (a plain byte store, idempotent).
@@ -104,18 +82,9 @@ __global__ __launch_bounds__(kThreads) void k_stale_build(const uint64_t* __rest
     const uint64_t k = key[i];
     uint64_t h = cap;
     if (k != kEmptyKey) {
-      h = row_hash(k);
-      const uint64_t hb = h & (8 * cap - 1);
+      const uint64_t hb = row_hash(k) & (8 * cap - 1);
       atomicOr(&bits[hb >> 5], 1u << (hb & 31));
-      h &= cap - 1;
-      for (;;) {
-        const unsigned long long prev =
-            atomicCAS(reinterpret_cast<unsigned long long*>(&table[h]),
-                      static_cast<unsigned long long>(kEmptyKey),
-                      static_cast<unsigned long long>(k));
-        if (prev == kEmptyKey || prev == k) break;
-        h = (h + 1) & (cap - 1);
-      }
+      h = keyset_insert(table, cap, k);
     } else {
       hit[cap + 1] = 1;
     }
@@ -176,17 +145,8 @@ __global__ __launch_bounds__(kThreads) void k_stale_probe(const uint64_t* __rest
 #pragma unroll
     for (int u = 0; u < kPRows; ++u) {
       if (!live[u]) continue;
-      uint64_t hh = h[u], sk = s[u];
-      // load < 1 (<= 1/2 up to 2^30 thumbnails): an empty slot ends every walk
-      for (;;) {
-        if (sk == k[u]) {
-          hit[hh] = 1;
-          break;
-        }
-        if (sk == kEmptyKey) break;
-        hh = (hh + 1) & (cap - 1);
-        sk = table[hh];
-      }
+      const uint64_t slot = keyset_find(table, cap, k[u], h[u], s[u]);
+      if (slot != ~0ull) hit[slot] = 1;
     }
   }
 }
@@ -252,19 +212,7 @@ __global__ __launch_bounds__(kThreads) void k_thumb_present(const uint64_t* __re
 #pragma unroll
     for (int u = 0; u < kPRows; ++u) {
       bool p = keyed[u] && k[u] == kEmptyKey && special;
-      if (live[u]) {
-        uint64_t hh = h[u], sk = s[u];
-        // load < 1 (<= 1/2 up to 2^30 thumbnails): an empty slot ends every walk
-        for (;;) {
-          if (sk == k[u]) {
-            p = true;
-            break;
-          }
-          if (sk == kEmptyKey) break;
-          hh = (hh + 1) & (cap - 1);
-          sk = table[hh];
-        }
-      }
+      if (live[u] && keyset_find(table, cap, k[u], h[u], s[u]) != ~0ull) p = true;
       const bool q = keyed[u] && e[u] != 0;
       if (in[u]) {
         const uint64_t i = i0 + static_cast<uint64_t>(u) * kThreads;
@@ -289,20 +237,20 @@ __global__ __launch_bounds__(kThreads) void k_thumb_present(const uint64_t* __re
   }
 }
 
-// The thumbnail list in tiles of kSRows x kThreads positions: position
+// The thumbnail list in tiles of kRows x kThreads positions: position
 // tile + k * kThreads + t, and (k, t) order is list order.  Bit k of the
 // result: this thread's k-th thumbnail is stale (its slot was not hit).
 __device__ __forceinline__ uint32_t stale_bits(const uint32_t* __restrict__ slot_of, uint64_t n,
                                                uint64_t tile, const uint8_t* __restrict__ hit) {
-  uint32_t sl[kSRows];
-  uint8_t m[kSRows];
+  uint32_t sl[kRows];
+  uint8_t m[kRows];
 #pragma unroll
-  for (int k = 0; k < kSRows; ++k) sl[k] = slot_of[min(tile + k * kThreads + threadIdx.x, n - 1)];
+  for (int k = 0; k < kRows; ++k) sl[k] = slot_of[min(tile + k * kThreads + threadIdx.x, n - 1)];
 #pragma unroll
-  for (int k = 0; k < kSRows; ++k) m[k] = hit[sl[k]];
+  for (int k = 0; k < kRows; ++k) m[k] = hit[sl[k]];
   uint32_t f = 0;
 #pragma unroll
-  for (int k = 0; k < kSRows; ++k)
+  for (int k = 0; k < kRows; ++k)
     f |= (tile + k * kThreads + threadIdx.x < n && m[k] == 0 ? 1u : 0u) << k;
   return f;
 }
@@ -311,18 +259,9 @@ __global__ __launch_bounds__(kThreads) void k_stale_count(const uint32_t* __rest
                                                           uint64_t n,
                                                           const uint8_t* __restrict__ hit,
                                                           uint32_t* __restrict__ cnt) {
-  __shared__ uint32_t sw[kSWaves];
-  const uint64_t tile = static_cast<uint64_t>(blockIdx.x) * kSTile;
-  uint32_t c = __popc(stale_bits(slot_of, n, tile, hit));
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
-  if (__lane_id() == 0) sw[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-    for (int w = 0; w < kSWaves; ++w) t += sw[w];
-    cnt[blockIdx.x] = t;
-  }
+  const uint64_t tile = static_cast<uint64_t>(blockIdx.x) * kTile;
+  const uint32_t t = compact::tile_count(stale_bits(slot_of, n, tile, hit));
+  if (threadIdx.x == 0) cnt[blockIdx.x] = t;
 }
 
 // stable compaction: tile b writes the positions of its stale thumbnails from
@@ -332,34 +271,14 @@ __global__ __launch_bounds__(kThreads) void k_stale_write(const uint32_t* __rest
                                                           const uint8_t* __restrict__ hit,
                                                           const uint32_t* __restrict__ offs,
                                                           uint32_t* __restrict__ out) {
-  __shared__ uint32_t off[kSRows][kSWaves];
-  const uint64_t tile = static_cast<uint64_t>(blockIdx.x) * kSTile;
-  const uint32_t lane = __lane_id(), w = threadIdx.x >> 6;
-  const uint64_t lt = (1ull << lane) - 1ull;
+  __shared__ uint32_t off[kRows][kWaves];
+  const uint64_t tile = static_cast<uint64_t>(blockIdx.x) * kTile;
+  const uint32_t w = threadIdx.x >> 6;
   const uint32_t f = stale_bits(slot_of, n, tile, hit);
-  uint32_t pre[kSRows];
+  uint32_t pre[kRows];
+  compact::tile_offsets(f, [&] { return offs[blockIdx.x]; }, off, pre);
 #pragma unroll
-  for (int k = 0; k < kSRows; ++k) {
-    const uint64_t b = __ballot(f >> k & 1u);
-    pre[k] = __popcll(b & lt);
-    if (lane == 0) off[k][w] = __popcll(b);
-  }
-  __syncthreads();
-  static_assert(kSRows * kSWaves == 64, "one wave scans the (row step, wave) counts");
-  if (threadIdx.x < 64) {  // (k, wave) order -- the array's order -- is list order
-    uint32_t* fl = &off[0][0];
-    const uint32_t a = fl[lane];
-    uint32_t inc = a;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t x = __shfl_up(inc, d);
-      if (lane >= static_cast<uint32_t>(d)) inc += x;
-    }
-    fl[lane] = offs[blockIdx.x] + inc - a;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < kSRows; ++k)
+  for (int k = 0; k < kRows; ++k)
     if (f >> k & 1u)
       out[off[k][w] + pre[k]] = static_cast<uint32_t>(tile + k * kThreads + threadIdx.x);
 }
@@ -376,15 +295,14 @@ __global__ __launch_bounds__(kThreads) void k_stale_dirs(const uint32_t* __restr
                                                          uint64_t n_bounds,
                                                          uint32_t* __restrict__ stale_start) {
   const uint32_t lane = __lane_id();
-  const uint64_t waves = static_cast<uint64_t>(gridDim.x) * kSWaves;
-  for (uint64_t d = static_cast<uint64_t>(blockIdx.x) * kSWaves + (threadIdx.x >> 6); d < n_bounds;
+  const uint64_t waves = static_cast<uint64_t>(gridDim.x) * kWaves;
+  for (uint64_t d = static_cast<uint64_t>(blockIdx.x) * kWaves + (threadIdx.x >> 6); d < n_bounds;
        d += waves) {
     const uint64_t p = min(static_cast<uint64_t>(dir_start[d]), n);
-    const uint64_t t = p / kSTile;
+    const uint64_t t = p / kTile;
     uint32_t c = 0;
-    for (uint64_t i = t * kSTile + lane; i < p; i += 64) c += hit[slot_of[i]] == 0 ? 1u : 0u;
-#pragma unroll
-    for (int x = 32; x > 0; x >>= 1) c += __shfl_xor(c, x);
+    for (uint64_t i = t * kTile + lane; i < p; i += 64) c += hit[slot_of[i]] == 0 ? 1u : 0u;
+    c = compact::wave_sum(c);
     if (lane == 0) stale_start[d] = offs[t] + c;
   }
 }
@@ -402,7 +320,7 @@ hipError_t stale_build_launch(const uint64_t* thumb_key, uint64_t n, void* ws, h
   if (e != hipSuccess) return e;
   e = hipMemsetAsync(w.bits, 0, w.cap, s);
   if (e != hipSuccess) return e;
-  if (n) k_stale_build<<<grid_for(n, kThreads), kThreads, 0, s>>>(thumb_key, n, w.table, w.cap,
+  if (n) k_stale_build<<<grid_for(n, kThreads, kMaxGrid), kThreads, 0, s>>>(thumb_key, n, w.table, w.cap,
                                                                    w.bits, w.slot_of, w.hit);
   return hipGetLastError();
 }
@@ -411,7 +329,7 @@ hipError_t stale_probe_launch(uint64_t n_thumbs, const uint64_t* col_key, const 
                               uint64_t rows, void* ws, hipStream_t s) {
   if (rows == 0) return hipSuccess;
   const StaleWs w = stale_ws(n_thumbs, ws);
-  const uint32_t grid = grid_for(rows, kThreads * kPRows);
+  const uint32_t grid = grid_for(rows, kThreads * kPRows, kMaxGrid);
   if (col_has)
     k_stale_probe<true><<<grid, kThreads, 0, s>>>(col_key, col_has, rows, w.table, w.cap, w.bits,
                                                   w.hit);
@@ -427,7 +345,7 @@ hipError_t thumb_present_launch(uint64_t n_thumbs, const uint64_t* key, const ui
                                 KTimer* timer) {
   if (rows == 0) return hipSuccess;
   const StaleWs w = stale_ws(n_thumbs, ws);
-  const uint32_t grid = grid_for(rows, kThreads * kPRows);
+  const uint32_t grid = grid_for(rows, kThreads * kPRows, kMaxGrid);
   KScope k(timer, "thumb_present", s);
 #define SD_THUMB_PRESENT(H, E)                                                                   \
   k_thumb_present<H, E><<<grid, kThreads, 0, s>>>(key, has, elig, rows, w.table, w.cap, w.bits, \
@@ -443,14 +361,14 @@ hipError_t thumb_present_launch(uint64_t n_thumbs, const uint64_t* key, const ui
 hipError_t stale_compact_launch(uint64_t n, const uint32_t* dir_start, uint32_t n_dirs,
                                 uint32_t* stale, uint32_t* stale_start, void* ws, hipStream_t s) {
   const StaleWs w = stale_ws(n, ws);
-  const uint64_t blocks = (n + kSTile - 1) / kSTile;
+  const uint64_t blocks = compact::tiles_for(n);
   const uint64_t bounds = static_cast<uint64_t>(n_dirs) + 1;
   if (blocks == 0) return hipMemsetAsync(stale_start, 0, 4 * bounds, s);
   k_stale_count<<<static_cast<uint32_t>(blocks), kThreads, 0, s>>>(w.slot_of, n, w.hit, w.cnt);
   scan::exclusive(w.cnt, blocks, w.cnt, w.tiles, nullptr, s);
   k_stale_write<<<static_cast<uint32_t>(blocks), kThreads, 0, s>>>(w.slot_of, n, w.hit, w.cnt,
                                                                    stale);
-  k_stale_dirs<<<grid_for(bounds, kSWaves), kThreads, 0, s>>>(w.slot_of, n, w.hit, w.cnt,
+  k_stale_dirs<<<grid_for(bounds, kWaves, kMaxGrid), kThreads, 0, s>>>(w.slot_of, n, w.hit, w.cnt,
                                                               dir_start, bounds, stale_start);
   return hipGetLastError();
 }

@@ -40,20 +40,14 @@ struct WorkWs {
 
 WorkWs work_ws(uint64_t n_thumbs, uint64_t n, bool with_work, void* ws) {
   WorkWs w;
-  uint8_t* p = static_cast<uint8_t*>(ws);
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    uint8_t* q = p ? p + o : nullptr;
-    o += (bytes + 255) / 256 * 256;
-    return q;
-  };
-  w.table = take(stale_workspace_bytes(n_thumbs));
-  w.present = take(n);
-  w.cand = take(with_work ? n : 0);
-  w.rep = reinterpret_cast<uint32_t*>(take(with_work ? 4 * n : 0));
-  w.counts = reinterpret_cast<uint32_t*>(take(with_work ? 4 * kDirs : 0));
-  w.shards = take(with_work ? thumb_workspace_bytes() : 0);
-  w.bytes = o;
+  Carve c(ws);
+  w.table = c.take(stale_workspace_bytes(n_thumbs));
+  w.present = c.take(n);
+  w.cand = c.take(with_work ? n : 0);
+  w.rep = c.take<uint32_t>(with_work ? n : 0);
+  w.counts = c.take<uint32_t>(with_work ? kDirs : 0);
+  w.shards = c.take(with_work ? thumb_workspace_bytes() : 0);
+  w.bytes = c.bytes();
   return w;
 }
 
@@ -137,8 +131,7 @@ hipError_t thumb_worklist_launch(const uint64_t* thumb_key, uint64_t n_thumbs, c
   if (e != hipSuccess) return e;
   {
     KScope k(timer, "thumb_work_mask", s);
-    const uint64_t g = (n + 4 * kThreads - 1) / (4 * kThreads);
-    k_work_mask<<<static_cast<uint32_t>(g < 2048 ? g : 2048), kThreads, 0, s>>>(w.rep, n, w.cand);
+    k_work_mask<<<grid_for(n, 4 * kThreads, 2048), kThreads, 0, s>>>(w.rep, n, w.cand);
   }
   e = thumbnail_shards_launch(reinterpret_cast<const uint8_t*>(key), w.cand, n, work, w.counts,
                               w.shards, s);
