@@ -11,6 +11,8 @@
 //!   -- core/src/object/media/thumbnail/mod.rs:204-359 (`thumbnailer.rs` here)
 //! * the indexer's rescan diff (to_create / to_update / to_remove)
 //!   -- core/src/location/indexer/walk.rs:309-381,624-636 (`indexer.rs` here)
+//! * what every directory of a location holds, for `size_in_bytes_bytes`
+//!   -- core/src/location/indexer/mod.rs:126-136 (`dir_sizes.rs` here)
 //! * sync ingest: which CRDT operations of a page apply
 //!   -- core/crates/sync/src/ingest.rs:114-233 (`sync.rs` here)
 //!
@@ -24,6 +26,7 @@
 
 pub mod burst;
 pub mod cas;
+pub mod dir_sizes;
 pub mod explorer;
 pub mod hash;
 pub mod identifier;

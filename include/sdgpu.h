@@ -854,6 +854,64 @@ int sdgpu_indexer_diff(sdgpu_ctx *ctx, const uint64_t *w_key, const uint8_t *w_f
                        uint32_t *matched, uint8_t *state, uint32_t *create, uint32_t *update,
                        uint32_t *remove, uint32_t *counts);
 
+/* (ABI 6, additive) Recursive directory sizes of ONE location in one call.
+ * The reference stores FilePathMetadata.size_in_bytes in
+ * file_path.size_in_bytes_bytes for every entry (core/src/location/indexer/
+ * mod.rs:126-136, 215-225) -- for a directory the size of its inode, which says
+ * nothing of the contents -- and orders and shows by that column
+ * (api/search.rs:85, api/locations.rs:66-100).  This call sums the files below
+ * every directory; storing the result is the caller's choice.
+ *   file_path rows of the location in ascending id order: d_r_dirkey[n_r] = the
+ *   key of the row's own materialized_path (as in sdgpu_indexer_diff);
+ *   d_r_selfkey[n_r] = for a directory row the key of its
+ *   materialized_path_for_children(), not read for a file row; d_r_flags[n_r]
+ *   (NULL = no directory rows; d_r_selfkey is then not read), bit 0 is_dir;
+ *   d_r_size[n_r] = size_in_bytes of a file row, not read for a directory row.
+ * Only equality of keys is used; the caller makes the answer exact by comparing
+ * the strings of every pair (i, d_parent[i]).
+ *   d_parent[i] = the lowest directory row j with r_selfkey[j] == r_dirkey[i],
+ *     or SDGPU_IDX_MISS when there is none (the location's top-level rows, and
+ *     rows whose directory row is absent).  Of two directory rows with one self
+ *     key the lowest owns the children; the other has none.
+ *   d_total[i] = r_size[i] for a file row; for a directory row the sum of r_size
+ *     over every file row below it, transitively through d_parent, modulo 2^64
+ *     (0 for an empty directory).
+ *   d_files[i] (may be NULL) = the file rows below a directory row; 0 for a file
+ *     row.
+ *   A directory row on a cycle of d_parent (a row that is its own parent, say: a
+ *     bad key or a collision) is unresolved: d_total = SDGPU_SIZE_UNRESOLVED,
+ *     d_files = 0xFFFFFFFF.  Every other directory row gets its exact answer; a
+ *     subtree that hangs below a cycle has its own totals, the cycle absorbs
+ *     them.
+ *   d_counts[4] = directory rows, directory rows resolved, rows with d_parent ==
+ *     SDGPU_IDX_MISS, the sum of d_total over those rows modulo 2^64 (the
+ *     location's size).  d_counts[1] < d_counts[0]: re-key with another salt.
+ * Every output is defined for every input and deterministic.  The keys 0 and
+ * ~0 are ordinary keys.  n_r == 0 is valid: the four counts are 0.
+ * -EINVAL: ctx or d_counts NULL; with n_r > 0 a NULL d_r_dirkey, d_r_size,
+ * d_parent or d_total, or d_r_flags without d_r_selfkey.  -E2BIG: n_r > 2^31.
+ * Both are decided before any device work.  The table of self keys in the
+ * context's workspace has 2 x (directory rows) slots rounded up to a power of
+ * two (at least 1024), 12 bytes a slot.  The device variant learns the number of
+ * directory rows on the device only, so it RESERVES the workspace for the
+ * worst case, every row a directory: with d_r_flags given about 12 bytes x (2 x
+ * n_r rounded up to a power of two) + 8 n_r (+ 4 n_r without d_files), of which
+ * the kernels touch the front part that the real number needs -- at 12.5 M rows
+ * 384 MiB + 100 MB reserved, 24 MiB of table touched for 1 M directories.  The
+ * host-array variant counts the flags and reserves exactly.  Asynchronous on
+ * `stream`, no synchronisation. */
+#define SDGPU_SIZE_UNRESOLVED 0xFFFFFFFFFFFFFFFFull
+int sdgpu_dir_sizes_device(sdgpu_ctx *ctx, const uint64_t *d_r_dirkey,
+                           const uint64_t *d_r_selfkey, const uint8_t *d_r_flags,
+                           const uint64_t *d_r_size, uint64_t n_r, uint32_t *d_parent,
+                           uint64_t *d_total, uint32_t *d_files, uint64_t *d_counts,
+                           void *stream);
+/* (ABI 6, additive) The same on host arrays: copy in, run, copy out; returns
+ * when done. */
+int sdgpu_dir_sizes(sdgpu_ctx *ctx, const uint64_t *r_dirkey, const uint64_t *r_selfkey,
+                    const uint8_t *r_flags, const uint64_t *r_size, uint64_t n_r,
+                    uint32_t *parent, uint64_t *total, uint32_t *files, uint64_t *counts);
+
 /* ---- sync ingest: which CRDT operations apply (ABI 6, additive) -----------------
  * The receiving half of library sync, core/crates/sync/src/ingest.rs.
  * receive_crdt_operation (ingest.rs:114-160) handles one op at a time, strictly

@@ -136,6 +136,9 @@ def _proto(L):
                                             c_vp, u64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
         "sdgpu_indexer_diff": (i32, [ctx, c_vp, c_vp, c_vp, u64, c_vp, u64, c_vp, c_vp, c_vp, c_vp,
                                      u64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+        "sdgpu_dir_sizes_device": (i32, [ctx, c_vp, c_vp, c_vp, c_vp, u64, c_vp, c_vp, c_vp, c_vp,
+                                         c_vp]),
+        "sdgpu_dir_sizes": (i32, [ctx, c_vp, c_vp, c_vp, c_vp, u64, c_vp, c_vp, c_vp, c_vp]),
         "sdgpu_oplog_create": (i32, [ctx, u64, P(c_vp)]),
         "sdgpu_oplog_destroy": (i32, [c_vp]),
         "sdgpu_oplog_clear": (i32, [c_vp, c_vp]),

@@ -458,6 +458,17 @@ hipError_t indexer_diff_launch(const IndexerIn& in, uint32_t* match, uint8_t* st
                                uint32_t* counts, void* ws, hipStream_t s,
                                KTimer* timer = nullptr);
 
+// ---- directory sizes (dir_sizes.hip) -------------------------------------------------
+// sdgpu_dir_sizes_device of include/sdgpu.h on checked arguments.  max_dirs: an
+// upper bound of the directory rows (the table itself is sized on the device
+// from their number); ws: dir_sizes_workspace_bytes bytes (own_files: the
+// caller passes no `files`), of which the call initialises all it reads.
+size_t dir_sizes_workspace_bytes(uint64_t n_r, uint64_t max_dirs, bool own_files);
+hipError_t dir_sizes_launch(const uint64_t* dirkey, const uint64_t* selfkey, const uint8_t* flags,
+                            const uint64_t* size, uint64_t n_r, uint64_t max_dirs,
+                            uint32_t* parent, uint64_t* total, uint32_t* files, uint64_t* counts,
+                            void* ws, hipStream_t s, KTimer* timer = nullptr);
+
 // ---- explorer search page (search.hip) -----------------------------------------------
 // The query of include/sdgpu.h (sdgpu_search_page_device) on device columns: tag
 // marks, filter + candidate records, radix select, final LDS sort.  ws:

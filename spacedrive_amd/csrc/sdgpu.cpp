@@ -1912,6 +1912,77 @@ int sdgpu_indexer_diff(sdgpu_ctx* c, const uint64_t* w_key, const uint8_t* w_fla
   return 0;
 }
 
+// Directory sizes (dir_sizes.hip).  The checks both variants share.
+static int dir_sizes_args(sdgpu_ctx* c, const uint64_t* dirkey, const uint64_t* selfkey,
+                          const uint8_t* flags, const uint64_t* size, uint64_t n_r,
+                          const uint32_t* parent, const uint64_t* total, const uint64_t* counts) {
+  if (!c || !counts) return -EINVAL;
+  if (n_r > (1ull << 31)) return -E2BIG;
+  if (n_r && (!dirkey || !size || !parent || !total || (flags && !selfkey))) return -EINVAL;
+  return 0;
+}
+
+int sdgpu_dir_sizes_device(sdgpu_ctx* c, const uint64_t* d_r_dirkey, const uint64_t* d_r_selfkey,
+                           const uint8_t* d_r_flags, const uint64_t* d_r_size, uint64_t n_r,
+                           uint32_t* d_parent, uint64_t* d_total, uint32_t* d_files,
+                           uint64_t* d_counts, void* stream) {
+  SD_TRY_RC(dir_sizes_args(c, d_r_dirkey, d_r_selfkey, d_r_flags, d_r_size, n_r, d_parent, d_total,
+                           d_counts));
+  std::lock_guard<std::mutex> g(c->mu);
+  SD_TRY(hipSetDevice(c->device));
+  hipStream_t s = pick(c, stream);
+  // the directory rows are counted on the device: any row may be one
+  const uint64_t max_dirs = d_r_flags ? n_r : 0;
+  if (n_r)
+    SD_TRY_RC(ensure_dev(c, c->link_ws, dir_sizes_workspace_bytes(n_r, max_dirs, !d_files)));
+  SD_TRY(dir_sizes_launch(d_r_dirkey, d_r_selfkey, d_r_flags, d_r_size, n_r, max_dirs, d_parent,
+                          d_total, d_files, d_counts, c->link_ws.p, s, c->kt()));
+  return 0;
+}
+
+int sdgpu_dir_sizes(sdgpu_ctx* c, const uint64_t* r_dirkey, const uint64_t* r_selfkey,
+                    const uint8_t* r_flags, const uint64_t* r_size, uint64_t n_r, uint32_t* parent,
+                    uint64_t* total, uint32_t* files, uint64_t* counts) {
+  SD_TRY_RC(dir_sizes_args(c, r_dirkey, r_selfkey, r_flags, r_size, n_r, parent, total, counts));
+  if (n_r == 0) {  // nothing to sum, decided on the host
+    memset(counts, 0, 4 * 8);
+    return 0;
+  }
+  uint64_t dirs = 0;
+  if (r_flags)
+    for (uint64_t i = 0; i < n_r; ++i) dirs += r_flags[i] & 1u;
+  std::lock_guard<std::mutex> g(c->mu);
+  SD_TRY(hipSetDevice(c->device));
+  hipStream_t s = pick(c, nullptr);
+  // workspace | the inputs | parent, total, files, counts in the context's link
+  // workspace
+  Carve cv;
+  cv.at(dir_sizes_workspace_bytes(n_r, dirs, false));
+  const size_t o_dk = cv.at(8 * n_r), o_sk = cv.at(r_flags ? 8 * n_r : 0);
+  const size_t o_fl = cv.at(r_flags ? n_r : 0), o_sz = cv.at(8 * n_r);
+  const size_t o_pa = cv.at(4 * n_r), o_to = cv.at(8 * n_r), o_fi = cv.at(4 * n_r);
+  const size_t o_cn = cv.at(4 * 8);
+  SD_TRY_RC(ensure_dev(c, c->link_ws, cv.bytes()));
+  uint8_t* base = static_cast<uint8_t*>(c->link_ws.p);
+  auto u64p = [&](size_t at) { return reinterpret_cast<uint64_t*>(base + at); };
+  auto u32p = [&](size_t at) { return reinterpret_cast<uint32_t*>(base + at); };
+  SD_TRY(hipMemcpyAsync(base + o_dk, r_dirkey, 8 * n_r, hipMemcpyHostToDevice, s));
+  if (r_flags) {
+    SD_TRY(hipMemcpyAsync(base + o_sk, r_selfkey, 8 * n_r, hipMemcpyHostToDevice, s));
+    SD_TRY(hipMemcpyAsync(base + o_fl, r_flags, n_r, hipMemcpyHostToDevice, s));
+  }
+  SD_TRY(hipMemcpyAsync(base + o_sz, r_size, 8 * n_r, hipMemcpyHostToDevice, s));
+  SD_TRY(dir_sizes_launch(u64p(o_dk), r_flags ? u64p(o_sk) : nullptr,
+                          r_flags ? base + o_fl : nullptr, u64p(o_sz), n_r, dirs, u32p(o_pa),
+                          u64p(o_to), u32p(o_fi), u64p(o_cn), base, s, c->kt()));
+  SD_TRY(hipMemcpyAsync(counts, base + o_cn, 4 * 8, hipMemcpyDeviceToHost, s));
+  SD_TRY(hipMemcpyAsync(parent, base + o_pa, 4 * n_r, hipMemcpyDeviceToHost, s));
+  SD_TRY(hipMemcpyAsync(total, base + o_to, 8 * n_r, hipMemcpyDeviceToHost, s));
+  if (files) SD_TRY(hipMemcpyAsync(files, base + o_fi, 4 * n_r, hipMemcpyDeviceToHost, s));
+  SD_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
 // Sync ingest (sync.hip; the handle and the runs are shard.cpp's).  The checks
 // both variants share: nothing of the handle is read before they pass.
 static bool ingest_args_ok(const sdgpu_oplog* x, const uint64_t* key, const uint64_t* tag,

@@ -262,7 +262,8 @@ class SearchColumns:
     """The call's columns for a FilePaths table: numpy on the host, tensors on
     the device (``rows()`` / ``objects()``), the extension dictionary (``ext_id``)
     and the order columns (``order_column``).  Dates and sizes are optional
-    per-row sequences (None = NULL).  dir_key is the indexer's key of the row's
+    per-row sequences (None = NULL); for directory rows size_in_bytes can take
+    the totals of dir_sizes.location_sizes.  dir_key is the indexer's key of the row's
     materialized_path (indexer.dir_keys, computed on the device)."""
 
     def __init__(self, table, attrs: ObjectAttrs | None = None, date_created=None,

@@ -68,6 +68,8 @@ def path_message(materialized_path: str, name: str, extension: str, salt: int = 
 
 
 def dir_message(children_path: str, salt: int = 0) -> bytes:
+    # a directory row (mp, name) has the children path mp + name + "/": its
+    # self key (dir_sizes.self_keys) is the key of that string
     return b"D" + bytes([salt]) + children_path.encode()
 
 
